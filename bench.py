@@ -7,6 +7,14 @@ cost). Inputs are resident in HBM before the timed region starts.
 
   value       PCG unknowns processed per second over the whole job:
               n_unknowns * lIterations * steps / wall time of the timed steps
+  ms_per_step wall time of the timed steps / --steps
+
+A plain run sets up, warms up, times --steps steps and prints the result line.
+--dump-outputs DIR then also writes what the last timed step left (the unknown arrays the
+Steps update in place, a fixed seeded sample of each array above 4 Mi elements, and the
+cost) as DIR/<name>.npy; the inputs are seeded, so two builds compare output for output.
+--full adds, after the timed steps:
+
   roofline    the dominant kernel (the in-loop J^T J p pass, iw_apply_res): its duration
               from HIP events on its launches (plan stream) over K more steps after the
               timed ones; init_kernel: the same for iw_jtf_apply
@@ -243,7 +251,12 @@ def parse():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--size", type=int, default=4096)
     ap.add_argument("--liter", type=int, default=10)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the roofline / per-kernel figures (K more "
+                         "instrumented steps), the pure apply and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step left (the unknowns and the cost) as DIR/<name>.npy")
     ap.add_argument("--workload", default="image_warping", choices=["image_warping", "shape_from_shading"])
     ap.add_argument("--dry-run", action="store_true",
                     help="print each rank's launch environment and slab rows as JSON; no GPU work")
@@ -428,6 +441,32 @@ def cpu_baseline_sfs(w, W, H, liter):
         "lm_iters_per_s": 1.0 / dt,
         "cpu_model": cpu_model(),
     }
+
+
+# --dump-outputs: at most this many elements of each array are written (fp32: 16 MiB per
+# array, so the headline's Offset + Angle stay well under 64 MB); a larger array is sampled
+# at fixed seeded positions, the same for every run with the same arguments
+DUMP_MAX_ELEMS = 1 << 22
+DUMP_SEED = 20240
+
+
+def dump_outputs(outdir, unknowns, cost, rank, world):
+    """What a caller of the timed path holds after its last step: the unknown arrays the
+    Steps updated in place (this rank's rows when the image is split) and the cost."""
+    import torch
+
+    os.makedirs(outdir, exist_ok=True)
+    tag = f"_rank{rank}" if world > 1 else ""
+    for name, t in unknowns.items():
+        flat = t.reshape(-1)
+        if flat.numel() > DUMP_MAX_ELEMS:
+            idx = np.random.default_rng(DUMP_SEED).integers(0, flat.numel(), size=DUMP_MAX_ELEMS)
+            flat = flat[torch.from_numpy(np.sort(idx)).to(flat.device)]
+        a = flat.cpu().numpy()
+        np.save(os.path.join(outdir, f"{name}{tag}.npy"), a.astype(np.float64 if a.dtype == np.float64 else np.float32))
+    np.save(os.path.join(outdir, f"cost{tag}.npy"), np.array([cost], dtype=np.float64))
+
+
 def main():
     args = parse()
     if args.gpus < 1:
@@ -495,9 +534,11 @@ def main():
     else:
         prm = [torch.from_numpy(lw[k]).cuda() for k in ("Offset", "Angle", "UrShape", "Constraints", "Mask")] + \
               [w["w_fitSqrt"], w["w_regSqrt"]]
-    # warmup, the K timed steps (no instrumentation), then K more steps with the apply
-    # kernel timed by HIP events on its launches (the roofline's kernel duration), so
+    unknowns = {"X": prm[len(w["params"])]} if sfs else {"Offset": prm[0], "Angle": prm[1]}
+    # warmup, the K timed steps (no instrumentation), then with --full K more steps with the
+    # apply kernel timed by HIP events on its launches (the roofline's kernel duration), so
     # the headline's timed region carries no instrumentation at all
+    # (nIterations leaves room for them either way: the cap does not change a step)
     total_steps = args.warmup + 2 * args.steps
     s.set_solver_params({"nIterations": total_steps + 1, "lIterations": args.liter})
     s.init(prm)
@@ -518,6 +559,51 @@ def main():
         t = torch.tensor([dt], device="cuda", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, unknowns, s.cost(), rank, world)
+    kind = "LM" if sfs else "GN"
+    n_ranks = api.load_library().OptAMD_CommSize(comm) if comm else 1   # what the solver ran on
+    rows = [H // world] * (world - 1) + [H - (world - 1) * (H // world)]
+    result = {
+        "metric": METRIC_SFS if sfs else METRIC,
+        "value": n_unknowns * args.liter * args.steps / dt,
+        "unit": "unknowns/s",
+        "n_gpus": n_ranks,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": 1000.0 * dt / args.steps,
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": f"synthetic (seeded {args.workload} inputs, SURVEY.md §8d)",
+        "config": {
+            "workload": f"{args.workload} {W}x{H} fp32 {kind}+PCG, lIterations={args.liter}",
+            "unknowns": n_unknowns,
+            "parallelism": (f"row-slabs x{n_ranks} of {rows[0]}" + (f"/{rows[-1]}" if rows[-1] != rows[0] else "")
+                            + f" rows (halo {HALO[args.workload]}; RCCL: {2 if sfs else 1} allreduce + 1 halo "
+                              "exchange per PCG iteration)" if n_ranks > 1 else "single"),
+        },
+        f"{kind.lower()}_iters_per_s": args.steps / dt,
+    }
+    if args.full:
+        full_figures(args, s, prm, w, sl, world, rank, sfs, n_unknowns, result)
+    if rank == 0:
+        print(json.dumps(result), flush=True)
+    s.close()
+    if comm:
+        api.load_library().OptAMD_CommDestroy(comm)
+    if dist:
+        dist.destroy_process_group()
+    return 0
+
+
+def full_figures(args, s, prm, w, sl, world, rank, sfs, n_unknowns, result):
+    """--full: K more instrumented steps for the roofline and per-kernel figures, the pure
+    apply, and the CPU baseline, added to the result line."""
+    import torch
+
+    W = H = args.size
     s.set_kernel_timing(2)  # HIP events on the apply kernel's launches only
     for _ in range(args.steps):
         s.step()
@@ -552,30 +638,7 @@ def main():
     p = torch.randn(n_local, device="cuda")
     Ap = torch.empty_like(p)
     pure_us = s.time_apply(prm, p, Ap, 20)
-    kind = "LM" if sfs else "GN"
-    n_ranks = api.load_library().OptAMD_CommSize(comm) if comm else 1   # what the solver ran on
-    rows = [H // world] * (world - 1) + [H - (world - 1) * (H // world)]
-    result = {
-        "metric": METRIC_SFS if sfs else METRIC,
-        "value": n_unknowns * args.liter * args.steps / dt,
-        "unit": "unknowns/s",
-        "n_gpus": n_ranks,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": 1000.0 * dt / args.steps,
-        "higher_is_better": True,
-        "scaling": "strong",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": f"synthetic (seeded {args.workload} inputs, SURVEY.md §8d)",
-        "config": {
-            "workload": f"{args.workload} {W}x{H} fp32 {kind}+PCG, lIterations={args.liter}",
-            "unknowns": n_unknowns,
-            "parallelism": (f"row-slabs x{n_ranks} of {rows[0]}" + (f"/{rows[-1]}" if rows[-1] != rows[0] else "")
-                            + f" rows (halo {HALO[args.workload]}; RCCL: {2 if sfs else 1} allreduce + 1 halo "
-                              "exchange per PCG iteration)" if n_ranks > 1 else "single"),
-        },
-        f"{kind.lower()}_iters_per_s": args.steps / dt,
+    result.update({
         "apply_unknowns_per_s": ch * npx * world / avg_apply_s,
         "pure_apply_us": pure_us,
         "pure_apply_unknowns_per_s": ch * npx * world / (pure_us * 1e-6),
@@ -597,7 +660,7 @@ def main():
             "limiter": (pmc_limiter(args.liter, first) if res == "pcg" and world == 1 and args.size == 4096
                         else None),
         },
-    }
+    })
     if n_init:
         init_s = (init_ms / 1e3) / n_init
         ibpp = init_bytes_per_px(args.liter, ap=res != "pcg")
@@ -618,14 +681,6 @@ def main():
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = (cpu_baseline_sfs(w, W, H, args.liter) if sfs
                                   else cpu_baseline(w, n_unknowns, args.liter))
-    if rank == 0:
-        print(json.dumps(result), flush=True)
-    s.close()
-    if comm:
-        api.load_library().OptAMD_CommDestroy(comm)
-    if dist:
-        dist.destroy_process_group()
-    return 0
 
 
 if __name__ == "__main__":

@@ -77,3 +77,31 @@ def intrinsic_ye():
 
 GENERATED_EXAMPLES = {"cotangent_mesh_smoothing": cotangent_head, "embedded_mesh_deformation": embedded_raptor,
                       "intrinsic_image_decomposition": intrinsic_ye, "volumetric_mesh_deformation": volumetric_head}
+
+
+# ---- the reference's example energy files, as records (tests/golden/reference_energies.json,
+# written by tests/golden/make_reference_energy_records.py from a reference checkout): the
+# files are program text and are not stored; what the front end made of each of them is.
+def reference_energy_record(name):
+    """{"describe_sha256", "signature_sha256", "templates", "family", "defines"} of the
+    reference's examples/<name>/<name>.t."""
+    import json
+
+    with open(os.path.join(GOLDEN, "reference_energies.json")) as f:
+        return json.load(f)[name]
+
+
+def describe_sha256(path):
+    """SHA-256 of an energy file's residual templates, as the records hold it."""
+    import hashlib
+
+    from opt_amd import api
+    return hashlib.sha256("\n".join(api.generic_describe(path)).encode()).hexdigest()
+
+
+def signature_sha256(path):
+    """SHA-256 of an energy file's structural signature, as the records hold it."""
+    import hashlib
+
+    from opt_amd import api
+    return hashlib.sha256(api.generic_signature(path).encode()).hexdigest()

@@ -71,5 +71,12 @@ def test_failed_rank_fails_the_launch():
     assert p.returncode != 0
 
 
+def test_full_and_dump_outputs_are_options(tmp_path):
+    """--full and --dump-outputs DIR parse; a dry run does no work, so it writes nothing."""
+    p = run(["--dry-run", "--full", "--dump-outputs", str(tmp_path / "out")])
+    assert p.returncode == 0, p.stderr
+    assert not (tmp_path / "out").exists()
+
+
 def test_bad_gpu_count():
     assert run(["--gpus", "0", "--dry-run"]).returncode == 2

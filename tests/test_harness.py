@@ -3,13 +3,12 @@ against the fixtures the pinned tests use, the results CSV and the option handli
 import os
 
 import numpy as np
-import pytest
 
 from opt_amd.harness import formats, problems, results
 from opt_amd.harness.__main__ import parser, read_config, resolve
 
-REF_DATA = "/root/reference/examples/data"
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+REF_DATA_GOLDEN = os.path.join(GOLDEN, "reference_data")   # SOURCES.md there names each file's origin
 
 
 def test_imagedump_round_trip_and_infinity_clamp(tmp_path):
@@ -96,10 +95,29 @@ def test_options_follow_argparser_and_config(tmp_path):
     assert o["backend"] == "backend_cpu" and not o["useOpt"] and o["stride"] == 1   # ArgParser.h defaults
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_DATA), reason="reference checkout not present")
-def test_builders_from_reference_data_match_fixtures():
+def reference_data(tmp_path):
+    """An examples/data folder as the reference lays it out, from the byte-for-byte copies
+    of its files in tests/golden/reference_data (the imagedumps stored gzipped)."""
+    import gzip
+    import shutil
+
+    dst = tmp_path / "data"
+    for d, _, files in os.walk(REF_DATA_GOLDEN):
+        out = dst / os.path.relpath(d, REF_DATA_GOLDEN)
+        out.mkdir(parents=True, exist_ok=True)
+        for f in files:
+            if f.endswith(".gz"):
+                with gzip.open(os.path.join(d, f), "rb") as src, open(out / f[:-3], "wb") as o:
+                    shutil.copyfileobj(src, o)
+            else:
+                shutil.copy(os.path.join(d, f), out / f)
+    return str(dst)
+
+
+def test_builders_from_reference_data_match_fixtures(tmp_path):
     from tests import reference_inputs as ri
 
+    REF_DATA = reference_data(tmp_path)
     a = problems.load_example("image_warping", REF_DATA)
     b = ri.image_warping_cat512()
     for k in ("Offset", "Angle", "UrShape", "Constraints", "Mask"):

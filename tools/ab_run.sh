@@ -13,7 +13,7 @@ for round in 1 2; do
     envs=""
     [ "$v" != "$n" ] && envs=$(echo "${v#*@}" | tr '@' ' ')
     tag=$(echo "$v" | tr '@=/' '___')
-    env $envs OPT_AMD_LIB=$lib timeout -k 10 120 python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline \
+    env $envs OPT_AMD_LIB=$lib timeout -k 10 120 python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline \
         > $O/$tag.$round.json 2> $O/$tag.$round.err || exit 1
     python3 -c "import json; d=json.load(open('$O/$tag.$round.json')); print('$v', $round, round(d['ms_per_step'],3), 'apply', round(d['roofline']['avg_us'],1), 'init', round(d.get('init_kernel',{}).get('avg_us',0),1))"
   done

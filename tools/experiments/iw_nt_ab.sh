@@ -8,7 +8,7 @@ OPT_AMD_IW_NT=7 timeout -k 10 300 python -u -m pytest tests/test_image_warping_g
     -x -q --timeout 120 --timeout-method thread > $O/test_nt7.log 2>&1
 for k in 1 2; do
   for V in 0 2 4 6; do
-    OPT_AMD_IW_NT=$V timeout -k 10 200 python bench.py --no-cpu-baseline --steps 20 --warmup 3 > $O/bench_${V}_$k.json 2> $O/bench_${V}_$k.err
+    OPT_AMD_IW_NT=$V timeout -k 10 200 python bench.py --full --no-cpu-baseline --steps 20 --warmup 3 > $O/bench_${V}_$k.json 2> $O/bench_${V}_$k.err
   done
 done
 echo DONE

@@ -9,8 +9,8 @@ R=$(pwd)
 TAG=${1:-r02z}
 O=$R/gpurun_out/$TAG
 mkdir -p $O
-timeout -k 10 300 python3 bench.py > $O/bench.json 2> $O/bench.err
-timeout -k 10 200 python3 bench.py --no-cpu-baseline --workload shape_from_shading > $O/bench_sfs.json 2> $O/bench_sfs.err
+timeout -k 10 300 python3 bench.py --full > $O/bench.json 2> $O/bench.err
+timeout -k 10 200 python3 bench.py --full --no-cpu-baseline --workload shape_from_shading > $O/bench_sfs.json 2> $O/bench_sfs.err
 cd /tmp && export TMPDIR=/tmp && cd $R
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/stats -o run --output-format csv -- \
     python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline > $O/stats.log 2>&1

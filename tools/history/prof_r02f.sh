@@ -5,8 +5,8 @@ set -e
 O=gpurun_out/r02f
 mkdir -p $O
 timeout -k 10 200 python -u -m pytest tests/test_rccl_multirank_gpu.py -m gpu -q -rs --timeout 240 --timeout-method thread > $O/rccl_test.txt 2>&1 || echo "rccl test rc=$?" >> $O/rccl_test.txt
-timeout -k 10 150 python bench.py --no-cpu-baseline > $O/bench.json 2> $O/bench.err
-timeout -k 10 150 python bench.py --no-cpu-baseline --workload shape_from_shading > $O/bench_sfs.json 2> $O/bench_sfs.err
+timeout -k 10 150 python bench.py --full --no-cpu-baseline > $O/bench.json 2> $O/bench.err
+timeout -k 10 150 python bench.py --full --no-cpu-baseline --workload shape_from_shading > $O/bench_sfs.json 2> $O/bench_sfs.err
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 for c in sfs optical_flow arap; do
   timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$c -o run -- python tools/bench_families.py --only $c --steps 5 > $O/fam_$c.json 2> $O/fam_$c.err

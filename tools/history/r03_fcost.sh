@@ -9,7 +9,7 @@ timeout -k 10 600 python3 -u -m pytest tests/test_image_warping_gpu.py -x -q \
     --timeout 300 --timeout-method thread > $O/tests.txt 2>&1
 for i in 1 2; do
   for c in 0 1; do
-    OPT_AMD_IW_FUSED_COST=$c timeout -k 10 300 python3 -u bench.py --steps 20 --warmup 3 --no-cpu-baseline > $O/b${c}_$i.json 2> $O/b${c}_$i.log
+    OPT_AMD_IW_FUSED_COST=$c timeout -k 10 300 python3 -u bench.py --full --steps 20 --warmup 3 --no-cpu-baseline > $O/b${c}_$i.json 2> $O/b${c}_$i.log
   done
 done
 cd /tmp && export TMPDIR=/tmp

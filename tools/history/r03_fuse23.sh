@@ -10,7 +10,7 @@ timeout -k 10 900 python3 -u -m pytest tests/test_sfs_gpu.py \
 tail -2 $O/tests.txt
 for round in 1 2; do
   for f in 0 1; do
-    OPT_AMD_FUSE23=$f timeout -k 10 200 python3 bench.py --workload shape_from_shading --no-cpu-baseline \
+    OPT_AMD_FUSE23=$f timeout -k 10 200 python3 bench.py --full --workload shape_from_shading --no-cpu-baseline \
         > $O/sfs_$f.$round.json 2> $O/sfs_$f.$round.err
     python3 -c "import json; d=json.load(open('$O/sfs_$f.$round.json')); print('fuse23=$f', $round, round(d['ms_per_step'],3), 'apply', round(d['roofline']['avg_us'],1))"
   done

@@ -5,7 +5,7 @@ set -e
 R=$(pwd)
 O=$R/gpurun_out/${1:-r03_measure}
 mkdir -p $O
-timeout -k 10 300 python3 bench.py > $O/bench.json 2> $O/bench.err
+timeout -k 10 300 python3 bench.py --full > $O/bench.json 2> $O/bench.err
 cd /tmp && export TMPDIR=/tmp && cd $R
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/stats -o run --output-format csv -- \
     python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline > $O/stats.log 2>&1

@@ -8,7 +8,7 @@ R=$(pwd)
 O=$R/gpurun_out/$1
 WL=${2:-image_warping}
 mkdir -p $O
-timeout -k 10 300 python3 bench.py --workload $WL > $O/bench_$WL.json 2> $O/bench_$WL.err
+timeout -k 10 300 python3 bench.py --full --workload $WL > $O/bench_$WL.json 2> $O/bench_$WL.err
 cd /tmp && export TMPDIR=/tmp && cd $R
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/stats_$WL -o run --output-format csv -- \
     python3 bench.py --workload $WL --steps 10 --warmup 2 --no-cpu-baseline > $O/stats_$WL.log 2>&1

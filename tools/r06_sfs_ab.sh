@@ -8,7 +8,7 @@ for round in 1 2; do
     envs=""
     [ "$v" != "${v%%@*}" ] && envs=$(echo "${v#*@}" | tr '@' ' ')
     tag=$(echo "$v" | tr '@=/' '___')
-    env $envs timeout -k 10 150 python3 bench.py --workload shape_from_shading --steps 10 --warmup 2 --no-cpu-baseline \
+    env $envs timeout -k 10 150 python3 bench.py --full --workload shape_from_shading --steps 10 --warmup 2 --no-cpu-baseline \
         > $O/$tag.$round.json 2> $O/$tag.$round.err || exit 1
     python3 -c "import json; d=json.load(open('$O/$tag.$round.json')); print('$v', $round, round(d['ms_per_step'],3), {k: round(x['avg_us'],1) for k, x in d.get('step_kernels', {}).items()})"
   done
