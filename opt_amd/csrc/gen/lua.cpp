@@ -1422,14 +1422,20 @@ void Interp::install() {
 // Per-step sample cache (round 6): a SampledImage read whose coordinates use the unknowns
 // and coordinates of ONE pixel (offset o) — optical_flow's I_hat(x + u(0,0), y + v(0,0)) — is
 // fixed while the PCG loop runs (the unknowns change only at the update). It becomes a
-// T-valued ComputedArray of its own (value + one gradient image per unknown access: the
+// T-valued internal image of its own (value + one gradient image per unknown access: the
 // sampled derivative images times the coordinates' derivatives, the same expressions
-// diff() forms for the Sample node, ad.sampledimage / o.t:3266-3280), evaluated once per
-// Step by the precompute kernels, and the residual reads it at offset o. The applies then
-// read two cached partials per pixel instead of re-sampling eight taps in every PCG
-// iteration (the reference re-samples, as the generic path did before). The values are
-// the same expressions on the same inputs. OPT_AMD_GEN_SAMPLE_CACHE=0 keeps the samples
-// in the residuals.
+// diff() forms for the Sample node, ad.sampledimage / o.t:3266-3280), filed with the
+// ComputedArrays so the residual reads it at offset o through the same machinery, but
+// tagged GComputed::per_step: it is a private cache of the bound arrays, not a
+// ComputedArray of the energy. Its precompute kernel therefore runs at the START of every
+// Step, from the unknowns and images bound at that Step (GenericOp::refresh_caches — the
+// caller may have rewritten or rebound any of them, Opt.h:64-65; the reference samples
+// inside the Step), and again with the ComputedArrays after each update and revert (the
+// end-of-Step cost and the next Step's LM model cost read it at the new unknowns). The
+// applies then read two cached partials per pixel instead of re-sampling eight taps in
+// every PCG iteration (the reference re-samples, as the generic path did before). The
+// values are the same expressions on the same inputs. OPT_AMD_GEN_SAMPLE_CACHE=0 keeps the
+// samples in the residuals; so does a sample whose images would not fit GenArgs::img.
 int Interp::cache_samples(int e) {
     const char* sv = getenv("OPT_AMD_GEN_SAMPLE_CACHE");
     if (sv && atoi(sv) == 0) return e;
@@ -1457,17 +1463,35 @@ int Interp::cache_samples(int e) {
                     ok = false;
                 }
             });
-        if (!ok || !reads || m_->images.size() + 3 > 16) return;   // GenArgs::img holds 16 images
+        if (!ok || !reads) return;
         const int neg[3] = {-off[0], -off[1], -off[2]};
         const int s0 = P().shift(id, neg);
         int img = -1;
         for (auto& c : sample_cache_)
             if (c.first == s0) img = c.second;
         if (img < 0) {
-            GImage im;
-            im.name = "sample_cache_" + std::to_string(sample_cache_.size());
             const std::vector<int> unk = m_->unknown_images();
             if (unk.empty()) return;
+            std::set<int> unkr;
+            P().visit(s0, [&](int nid, const Node& q) {
+                if (q.op == Op::Read && q.slot < 0 && m_->images[q.i].unknown) unkr.insert(nid);
+            });
+            // GenArgs::img holds 16 images: the value image and one gradient image per
+            // unknown access with a non-constant derivative must all fit, else the sample
+            // stays in the residual
+            std::vector<GGrad> grads;
+            size_t need = 1;
+            for (int u : unkr) {
+                GGrad g;
+                g.ch = 0;
+                g.u = u;
+                g.expr = P().diff(s0, u);
+                if (!P().is_const(g.expr)) ++need;
+                grads.push_back(g);
+            }
+            if (m_->images.size() + need > 16) return;
+            GImage im;
+            im.name = "sample_cache_" + std::to_string(sample_cache_.size());
             im.dims = m_->images[unk[0]].dims;
             im.channels = 1;
             im.internal = im.tvalued = true;
@@ -1476,19 +1500,12 @@ int Interp::cache_samples(int e) {
             GComputed c;
             c.image = img;
             c.expr = {s0};
-            std::set<int> unkr;
-            P().visit(s0, [&](int nid, const Node& q) {
-                if (q.op == Op::Read && q.slot < 0 && m_->images[q.i].unknown) unkr.insert(nid);
-            });
-            for (int u : unkr) {
-                GGrad g;
-                g.ch = 0;
-                g.u = u;
-                g.expr = P().diff(s0, u);
+            c.per_step = true;
+            for (GGrad& g : grads) {
                 int gnode = g.expr;
                 if (!P().is_const(g.expr)) {
                     GImage gi;
-                    gi.name = im.name + "_d_" + std::to_string(u);
+                    gi.name = im.name + "_d_" + std::to_string(g.u);
                     gi.dims = im.dims;
                     gi.internal = gi.tvalued = true;
                     m_->images.push_back(gi);
@@ -1496,7 +1513,7 @@ int Interp::cache_samples(int e) {
                     const int z[3] = {0, 0, 0};
                     gnode = P().read(g.gimg, 0, z);
                 }
-                P().add_computed_grad(img, 0, u, gnode);
+                P().add_computed_grad(img, 0, g.u, gnode);
                 c.grads.push_back(g);
             }
             m_->computed.push_back(c);

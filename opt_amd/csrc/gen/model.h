@@ -35,6 +35,8 @@ struct GComputed {
     std::vector<int> expr;         // per channel
     std::vector<GGrad> grads;
     int lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};   // bbox of the expression (bboxforexpression)
+    bool per_step = false;         // a private cache of bound arrays (lua.cpp cache_samples),
+                                   // not a ComputedArray of the energy: also rebuilt at Step start
 };
 struct GParam { std::string name; std::string type; int index = -1; };
 struct GGraph {

@@ -385,12 +385,20 @@ public:
     void precompute(hipStream_t s) {
         for (hipFunction_t f : k_pre_) launch(f, s, {&a_});
     }
-    // The transcendental caches (the precompute kernels after the ComputedArrays' ones:
-    // the centred cache image, the graph record cache) from the arrays bound at this Step
-    // (StencilPlan::step; HasRefreshCaches). Returns whether any ran.
+    // The private caches of values derived from the bound arrays, from the arrays bound at
+    // this Step (StencilPlan::step; HasRefreshCaches): the per-step sample caches among the
+    // ComputedArrays' kernels (GComputed::per_step) and the transcendental caches (the
+    // precompute kernels after the ComputedArrays' ones: the centred cache image, the graph
+    // record cache). The energy's own ComputedArrays are not touched: they keep the
+    // reference's schedule. Returns whether any ran.
     bool refresh_caches(hipStream_t s) {
-        for (size_t k = m_.computed.size(); k < k_pre_.size(); ++k) launch(k_pre_[k], s, {&a_});
-        return k_pre_.size() > m_.computed.size();
+        bool ran = false;
+        for (size_t k = 0; k < k_pre_.size(); ++k)
+            if (k >= m_.computed.size() || m_.computed[k].per_step) {
+                launch(k_pre_[k], s, {&a_});
+                ran = true;
+            }
+        return ran;
     }
     // ComputedArray values and gradient images: exchanged after every precompute
     void computed_planes(std::vector<HaloPlane>& v) const {

@@ -151,11 +151,15 @@ template <class Op>
 struct HasSlabRefusal<Op, std::void_t<decltype(std::declval<const Op&>().slab_refusal())>> : std::true_type {};
 
 // Ops that keep private per-step caches of values derived from the bound arrays
-// (GenericOp: transcendentals of centred and graph-slot reads): refresh_caches(stream)
-// recomputes them from the arrays as bound at THIS Step. The reference evaluates those
-// values inline from the arrays at every Step (setGPUptr, solverGPUGaussNewton.t:2001), so
-// a caller may rewrite or rebind arrays between Steps (Opt.h:64-65); ComputedArrays
-// themselves keep the reference's schedule (init, after update, after revert).
+// (GenericOp: transcendentals of centred and graph-slot reads, and the sample caches —
+// sampled images and their gradient images at the unknowns' coordinates): refresh_caches
+// (stream) recomputes them at the start of every Step from the arrays as bound at THIS
+// Step. The reference evaluates those values inline from the arrays at every Step
+// (setGPUptr, solverGPUGaussNewton.t:2001), so a caller may rewrite or rebind arrays —
+// the unknowns included — between Steps (Opt.h:64-65). Caches that depend on the unknowns
+// are rebuilt after each update and revert as well (they ride with precompute). The
+// energy's ComputedArrays themselves keep the reference's schedule (init, after update,
+// after revert) and are NOT refreshed at Step start.
 template <class Op, class = void>
 struct HasRefreshCaches : std::false_type {};
 template <class Op>

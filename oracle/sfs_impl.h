@@ -4,7 +4,8 @@
  * arrays (D_i, Im, edge masks) stay float, as the harness passes them
  * (examples/shared/OptSolver.h:20-28). Instantiated for REAL = float and double by
  * oracle/sfs.c. Constants are the energy's Lua numbers cast to opt_float; the three
- * weights are square-rooted in float, as the runtime passes float parameters.
+ * weights arrive as float parameters, are converted to opt_float where they are read
+ * (API/src/o.t:2430) and square-rooted in opt_float (the energy's sqrt(Param)).
  */
 #define CAT2(a, b) a##b
 #define CAT(a, b) CAT2(a, b)
@@ -111,7 +112,8 @@ static int FN(eval_res)(const FN(sfs_ctx)* c, int t, int x, int y, FN(res_t)* r)
     r->ncomp = (t == 3) ? 3 : 1;
     if (!FN(sin_)(c, x, y)) return 0;
     const long long k = (long long)y * c->W + x;
-    const REAL wp = (REAL)sqrtf((float)c->wp), ws = (REAL)sqrtf((float)c->ws), wg = (REAL)sqrtf((float)c->wg);
+    /* (REAL)sqrt((double)w): the correctly rounded square root in REAL (for float, sqrtf) */
+    const REAL wp = (REAL)sqrt((double)c->wp), ws = (REAL)sqrt((double)c->ws), wg = (REAL)sqrt((double)c->wg);
     if (t == 0) {
         if (!FN(DV)(c, x, y)) return 0;
         r->val[0] = wp * (c->X[k] - c->D[k]);

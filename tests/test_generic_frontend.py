@@ -264,3 +264,41 @@ def test_apply_variant_rule(monkeypatch, name, kernel):
         name = name.split(":")[0]
     head = api.generic_source(E(name)).splitlines()[0]
     assert head.startswith("// apply: " + kernel)
+
+
+def _sample_at_image_limit(n_fill):
+    """An energy with 4 + n_fill declared images whose one SampledImage read takes its
+    coordinates from three unknown channels: the sample cache would need 1 value image + 3
+    gradient images (every d sample / d channel is a sampled derivative image)."""
+    txt = ('local W,H = Dim("W",0), Dim("H",1)\nlocal X = Unknown("X", opt_float3,{W,H},0)\n'
+           'local I = Array("I", opt_float,{W,H},1)\nlocal Ix = Array("Ix", opt_float,{W,H},2)\n'
+           'local Iy = Array("Iy", opt_float,{W,H},3)\n')
+    for k in range(n_fill):
+        txt += 'local F%d = Array("F%d", opt_float,{W,H},%d)\n' % (k, k, 4 + k)
+    txt += ('local S = SampledImage(I, Ix, Iy)\n'
+            'Energy(S(Index(0) + X(0,0,0) + X(0,0,2), Index(1) + X(0,0,1)))\n')
+    for k in range(n_fill):
+        txt += 'Energy(X(0,0,%d) - F%d(0,0))\n' % (k % 3, k)
+    return txt
+
+
+def test_sample_cache_falls_back_when_its_images_do_not_fit(tmp_path):
+    """The kernel argument block holds 16 images. cache_samples (lua.cpp) must count the
+    value image AND every non-constant gradient image before it caches a sample: with 13
+    declared images and three unknown channels in the sample's coordinates the cache needs
+    4 more (17 > 16), so the sample stays in the residual (the gather apply, as with
+    OPT_AMD_GEN_SAMPLE_CACHE=0) and the problem is still accepted; with 12 declared images
+    the cache fits exactly and the strip apply serves it."""
+    full = _write(tmp_path, "full.t", _sample_at_image_limit(9))
+    head = api.generic_source(full).splitlines()[0]
+    assert head.startswith("// apply: gen_apply ")
+    assert "gen_precompute_0" not in api.generic_source(full)
+    lib, st, pr = _define(full)
+    assert pr   # not refused with "more than 16 images"
+    lib.Opt_ProblemDelete(st, pr)
+    api.generic_compile_check(full)
+    fits = _write(tmp_path, "fits.t", _sample_at_image_limit(8))
+    assert api.generic_source(fits).splitlines()[0].startswith("// apply: gen_apply_strip")
+    lib, st, pr = _define(fits)
+    assert pr
+    lib.Opt_ProblemDelete(st, pr)

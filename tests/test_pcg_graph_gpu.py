@@ -89,6 +89,27 @@ def test_generated_graph_replay_follows_rebound_buffers(monkeypatch):
     np.testing.assert_array_equal(o_graph, o_eager)
 
 
+def _generated_of_mutations(monkeypatch, graph, how):
+    """Generated optical_flow, fp64 GN, the mutations of tests/test_step_rebinding_gpu.py
+    (flow edits, new target images, a new weight) between steps: the per-Step sample cache
+    is rebuilt outside the captured PCG loop, the replay reads it."""
+    from tests.test_step_rebinding_gpu import CASES, _run
+
+    monkeypatch.setenv("OPT_AMD_NO_GRAPH", "0" if graph else "1")
+    monkeypatch.setenv("OPT_AMD_GENERIC", "1")
+    costs, unk = _run(CASES["of64x48"], True, how, family="generic")
+    return list(costs), unk["X"]
+
+
+@pytest.mark.parametrize("how", ["in_place", "rebind"])
+def test_generated_optical_flow_graph_replay_follows_changed_arrays(monkeypatch, how):
+    c_eager, x_eager = _generated_of_mutations(monkeypatch, False, how)
+    c_graph, x_graph = _generated_of_mutations(monkeypatch, True, how)
+    assert len(c_eager) == 4
+    assert c_graph == c_eager
+    np.testing.assert_array_equal(x_graph, x_eager)
+
+
 def _embedded_rebinding(monkeypatch, graph):
     """A graph energy whose declarations the simple parser cannot read (RotMatrix): new
     edge arrays in a different order, on new buffers, between steps."""
