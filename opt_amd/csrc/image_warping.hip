@@ -94,13 +94,10 @@ struct Args {
     // tb1 + t - tn0 (whole domain: 0, nstrips * nrowblocks, 0; the slab plans launch the
     // interior row blocks and the two boundary row blocks separately to overlap the halo)
     int tb0, tn0, tb1;
-    // side != 0 (geom): the block's four waves walk the SAME rows over four adjacent strips
-    // (tile = row chunk x group of 4 strips) instead of four stacked row ranges of one strip
+    // side != 0: the block's four waves walk the SAME rows over four adjacent strips (tile =
+    // row chunk x group of 4 strips) instead of four stacked row ranges of one strip. Only
+    // launch_pcg sets it (iw_pcg, geom_fused); every other launch leaves it 0.
     int side;
-    // alt != 0 (iw_pcg): waves of odd row chunks ((y0 - y_lo) / rows odd) walk their rows
-    // bottom to top, so the two waves on either side of every chunk boundary read the shared
-    // halo rows at the same time (both at their start or both at their end)
-    int alt;
     // rev != 0 (round 6, OPT_AMD_IW_MALL_REV): the launch takes its tiles in reverse order
     // (logical tile gridDim - 1 - remapped block), so it starts where the previous kernel of
     // the Step ended, on the vectors that kernel wrote last and that still sit in the 256 MB
@@ -195,6 +192,10 @@ __device__ __forceinline__ WaveGeom geom(const Args<T>& a) {
     // derived from it is then scalar arithmetic, not per-lane VALU work
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
     int strip, ychunk;
+    // Args::side is 0 in every launch of a kernel on this geometry (only launch_pcg sets it,
+    // and iw_pcg runs on geom_fused). The branch stays for the code it makes: without it
+    // iw_apply_res<double, 2, 2, 1> takes 8 AGPRs instead of 4 beside its 252 VGPRs and drops
+    // from 2 waves per SIMD to 1.
     if (a.side) {
         const int ng = (a.nstrips + kBlock / kWave - 1) / (kBlock / kWave);
         strip = (t % ng) * (kBlock / kWave) + w;
@@ -1118,17 +1119,16 @@ struct HRow {
     vec2_t<T> r;
     T rt, w0, w2;
 };
-// SNT: streaming stores. The 60-column strips store 240-byte row segments that straddle
-// cache lines shared with the neighbouring strips; plain stores let the L2 merge them.
+// Plain stores: the 60-column strips store 240-byte row segments that straddle cache lines
+// shared with the neighbouring strips, and the L2 merges them.
 // U2: two rows per loop trip with the row records swapping roles (no register copies, but
 // more VGPRs live: 138-168 against 120-142, 3 waves per SIMD instead of 4 on the odd passes)
-// PF2 (with U2): two raw rows in flight per wave instead of one.
 // REC: the REC layout (Args::S): pin == rin is the record of iteration i-1, pout == rout
 // that of iteration i, both halves stored by stage A; pin2 the record of iteration i-2.
 // PRC (passes without P0): the angle preconditioner recomputed from the stencil's geometry
 // (diag_a2 over the four edges, in iw_jtf's order, pre_angle) instead of read: bitwise the
 // stored value, 4 B/px less per pass.
-template <typename T, int DM, int E, bool P0, bool SNT, bool U2, bool PF2, bool REC, bool PRC = false>
+template <typename T, int DM, int E, bool P0, bool U2, bool REC, bool PRC = false>
 __device__ __forceinline__ void iw_pcg_body(const Args<T>& a, const T* __restrict__ pin, const T* __restrict__ rin,
                                             const T* __restrict__ pre, T* __restrict__ pout, T* rout,
                                             T* __restrict__ delta, double* __restrict__ sc, int prev,
@@ -1228,25 +1228,20 @@ __device__ __forceinline__ void iw_pcg_body(const Args<T>& a, const T* __restric
             if (!h.act) { h.p = (vec2_t<T>)0; h.pt = 0; }
             return h;
         };
-        // the walk: row Y(k), k = 0 .. n - 1 (halo rows Y(-2), Y(-1), Y(n), Y(n + 1)); top to
-        // bottom, or with Args::alt on odd row chunks bottom to top — the same chain with
-        // "the next row" the one above (apply_ap2's carries then come from below: the same
-        // residual values, summed in the mirrored order)
+        // the walk: rows y0 + k, k = 0 .. n - 1 (halo rows y0 - 2, y0 - 1, y1, y1 + 1), top to bottom
         const int n = g.y1 - g.y0;
-        const bool up = a.alt && (((g.y0 - a.dom.y_lo) / a.rows) & 1);
-        auto Y = [&](int k) { return up ? g.y1 - 1 - k : g.y0 + k; };
-        const GRow<T> g0 = fin(raw(Y(-2)));
-        GRow<T> qc = fin(raw(Y(-1)));
-        GRow<T> qd = fin(raw(Y(0)));
+        const GRow<T> g0 = fin(raw(g.y0 - 2));
+        GRow<T> qc = fin(raw(g.y0 - 1));
+        GRow<T> qd = fin(raw(g.y0));
         ka = acarry_init(g0.p, g0.pt, g0.c, g0.s, g0.u, g0.act(), qc.p, qc.pt, qc.c, qc.s, qc.u, qc.act(), wr);
         if constexpr (PRC)
             dthm_a = g0.act() && qc.act() ? diag_a2(qc.c, qc.s, qc.u.x, qc.u.y, g0.u.x, g0.u.y, wr2) : (T)0;
-        HRow<T> hup = stage_a(qc, qd, Y(-1));
+        HRow<T> hup = stage_a(qc, qd, g.y0 - 1);
         qc = qd;
-        qd = fin(raw(Y(1)));
-        HRow<T> hc = stage_a(qc, qd, Y(0));
+        qd = fin(raw(g.y0 + 1));
+        HRow<T> hc = stage_a(qc, qd, g.y0);
         qc = qd;
-        qd = fin(raw(Y(2)));
+        qd = fin(raw(g.y0 + 2));
         ACarry<T> kb = acarry_init(hup.p, hup.pt, hup.c, hup.s, hup.u, hup.act, hc.p, hc.pt, hc.c, hc.s, hc.u, hc.act, wr);
         // stage B at row y: Ap_i from (cur = row y, dn = row y+1), stores p_i, the three sums
         auto stage_b = [&](const HRow<T>& cur, const HRow<T>& dn, int y) {
@@ -1272,59 +1267,39 @@ __device__ __forceinline__ void iw_pcg_body(const Args<T>& a, const T* __restric
         // trip at row y, q0 / q1 hold rows y+1 / y+2 and h0 row y
         if constexpr (!U2) {
             for (int k = 0; k < n; ++k) {
-                const GRaw<T> nx = raw(Y(min(k + 3, n + 1)));
-                const HRow<T> hd = stage_a(qc, qd, Y(k + 1));
-                stage_b(hc, hd, Y(k));
+                const GRaw<T> nx = raw(g.y0 + min(k + 3, n + 1));
+                const HRow<T> hd = stage_a(qc, qd, g.y0 + k + 1);
+                stage_b(hc, hd, g.y0 + k);
                 hc = hd;
                 qc = qd;
                 qd = fin(nx);
             }
-        } else if constexpr (PF2) {
+        } else {
             GRow<T> q0 = qc, q1 = qd;
             HRow<T> h0 = hc, h1;
-            GRaw<T> na = raw(Y(min(3, n + 1))), nb = raw(Y(min(4, n + 1)));
             for (int k = 0; k < n; k += 2) {
-                h1 = stage_a(q0, q1, Y(k + 1));
-                stage_b(h0, h1, Y(k));
-                q0 = fin(na);
+                // stage A needs rows up to y1 + 1; the last trip re-reads that row (an L2 hit)
+                const GRaw<T> n1 = raw(g.y0 + min(k + 3, n + 1));
+                h1 = stage_a(q0, q1, g.y0 + k + 1);
+                stage_b(h0, h1, g.y0 + k);
+                q0 = fin(n1);
                 if (k + 1 >= n) break;
-                na = raw(Y(min(k + 5, n + 1)));
-                h0 = stage_a(q1, q0, Y(k + 2));
-                stage_b(h1, h0, Y(k + 1));
-                q1 = fin(nb);
-                nb = raw(Y(min(k + 6, n + 1)));
+                const GRaw<T> n2 = raw(g.y0 + min(k + 4, n + 1));
+                h0 = stage_a(q1, q0, g.y0 + k + 2);
+                stage_b(h1, h0, g.y0 + k + 1);
+                q1 = fin(n2);
             }
-        } else {
-        GRow<T> q0 = qc, q1 = qd;
-        HRow<T> h0 = hc, h1;
-        for (int k = 0; k < n; k += 2) {
-            // stage A needs rows up to Y(n + 1); the last trip re-reads that row (an L2 hit)
-            const GRaw<T> n1 = raw(Y(min(k + 3, n + 1)));
-            h1 = stage_a(q0, q1, Y(k + 1));
-            stage_b(h0, h1, Y(k));
-            q0 = fin(n1);
-            if (k + 1 >= n) break;
-            const GRaw<T> n2 = raw(Y(min(k + 4, n + 1)));
-            h0 = stage_a(q1, q0, Y(k + 2));
-            stage_b(h1, h0, Y(k + 1));
-            q1 = fin(n2);
-        }
         }
     }
     double v[4] = {(double)rzd, (double)papd, (double)rapd, (double)apapd};
     block_reduce_publish<4>(v, rs, g.tile);
 }
-template <typename T, int DM, int E = 0, bool P0 = false, bool SNT = false, bool U2 = false, bool PF2 = false,
-          bool REC = false, bool PRC = false>
-#ifndef IW_PCG_WAVES
-#define IW_PCG_WAVES 1   // A/B builds (tools/ab_build.sh): the minimum waves per SIMD iw_pcg is held to
-#endif
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(IW_PCG_WAVES))) void iw_pcg(Args<T> a, const T* __restrict__ pin, const T* __restrict__ rin,
+template <typename T, int DM, int E = 0, bool P0 = false, bool U2 = false, bool REC = false, bool PRC = false>
+__global__ __launch_bounds__(kBlock) void iw_pcg(Args<T> a, const T* __restrict__ pin, const T* __restrict__ rin,
                                                  const T* __restrict__ pre, T* __restrict__ pout, T* rout,
                                                  T* __restrict__ delta, double* __restrict__ sc, int prev,
                                                  double base_scale, ReduceSlot rs, const T* pin2 = nullptr) {
-    iw_pcg_body<T, DM, E, P0, SNT, U2, PF2, REC, PRC>(a, pin, rin, pre, pout, rout, delta, sc, prev, base_scale, rs,
-                                                      pin2);
+    iw_pcg_body<T, DM, E, P0, U2, REC, PRC>(a, pin, rin, pre, pout, rout, delta, sc, prev, base_scale, rs, pin2);
 }
 
 // ------------------------------------------------------------- value rows
@@ -1621,9 +1596,11 @@ struct FRow {          // a finished row of the fused kernel's apply window
         return v;
     }
 };
+// Plain stores: the 60-column strips store 240-B row segments that share cache lines with
+// the neighbouring strips, and the L2 merges them.
 // REC: r_0 (and p_0 unless pout is null) go to the record r, UrShape / the angle / pre_t
 // to the S record (Args::S); pre is not written
-template <typename T, int NT = 2, bool REC = false>
+template <typename T, bool REC = false>
 __device__ __forceinline__ void iw_jtf_apply_body(const Args<T>& a, T* __restrict__ r, T* __restrict__ pre,
                                                   T* __restrict__ pout, T* __restrict__ Ap, ReduceSlot rs) {
     IW_PRE_TABLE(a);
@@ -1645,16 +1622,16 @@ __device__ __forceinline__ void iw_jtf_apply_body(const Args<T>& a, T* __restric
             if constexpr (REC) {   // p_0 = pre r_0 as FRow::p / pt form it (whole records: a
                 // record left partly unwritten costs a partial-line write per line)
                 const ROff<T> ro(i);
-                stb<(NT & 2) != 0>(r, ro.r, rv);
+                stb<false>(r, ro.r, rv);
                 vec2_t<T> tt;
                 tt.x = o.rt; tt.y = opaque(o.wt * o.rt);
-                stb<(NT & 2) != 0>(r, ro.t, tt);
-                stb<(NT & 2) != 0>(r, ro.p, opaque(o.wo * rv));
-                st_srec<(NT & 2) != 0>(a.S, ro.s, cur.ux, cur.uy, cur.t, o.wt);
+                stb<false>(r, ro.t, tt);
+                stb<false>(r, ro.p, opaque(o.wo * rv));
+                st_srec<false>(a.S, ro.s, cur.ux, cur.uy, cur.t, o.wt);
             } else {
                 const POff<T> off(i, tb);
-                stb<(NT & 2) != 0>(r, off.xy, rv); stb<(NT & 2) != 0>(r, off.t, o.rt);
-                stb<(NT & 2) != 0>(pre, off.s, o.wt);
+                stb<false>(r, off.xy, rv); stb<false>(r, off.t, o.rt);
+                stb<false>(pre, off.s, o.wt);
             }
             if (cur.act) rzdot += wdot3(o.wo, o.rx, o.rx, o.wo, o.ry, o.ry, o.wt, o.rt, o.rt);
         }
@@ -1693,10 +1670,10 @@ __device__ __forceinline__ void iw_jtf_apply_body(const Args<T>& a, T* __restric
                 const unsigned iy = (unsigned)a.dom.off(g.x, y);
                 const POff<T> off(iy, tb);
                 if (Ap) {   // null when lIterations == 1 or when iw_pcg recomputes Ap_0 (always with REC)
-                    stb<(NT & 2) != 0>(Ap, off.xy, ao); stb<(NT & 2) != 0>(Ap, off.t, aot);
+                    stb<false>(Ap, off.xy, ao); stb<false>(Ap, off.t, aot);
                 }
                 if (!REC && pout) {   // null when the loop forms p_0 from r_0 itself (lIterations >= 3)
-                    stb<(NT & 2) != 0>(pout, off.xy, cp); stb<(NT & 2) != 0>(pout, off.t, cpt);
+                    stb<false>(pout, off.xy, cp); stb<false>(pout, off.t, cpt);
                 }
                 papdot += dot3(cp.x, ao.x, cp.y, ao.y, cpt, aot);
                 // PCGStep2's weights: pre, or 1 without a preconditioner
@@ -1713,10 +1690,10 @@ __device__ __forceinline__ void iw_jtf_apply_body(const Args<T>& a, T* __restric
     block_reduce_publish<4>(v, rs, g.tile);
 }
 // (the compiler's 112-114 VGPRs give 4 waves per SIMD; forcing 5 spills: 504 vs 373 us)
-template <typename T, int NT = 2, bool REC = false>
+template <typename T, bool REC = false>
 __global__ __launch_bounds__(kBlock) void iw_jtf_apply(Args<T> a, T* __restrict__ r, T* __restrict__ pre,
                                                        T* __restrict__ pout, T* __restrict__ Ap, ReduceSlot rs) {
-    iw_jtf_apply_body<T, NT, REC>(a, r, pre, pout, Ap, rs);
+    iw_jtf_apply_body<T, REC>(a, r, pre, pout, Ap, rs);
 }
 
 // ----------------------------------------------------------------- cost kernel
@@ -2056,7 +2033,7 @@ __global__ __launch_bounds__(kBlock) void iw_update(Args<T> a, T* __restrict__ O
 constexpr int kAllPMax = 16;
 // (L a template parameter: the loop unrolls with every load of a pixel issued back to back)
 // P0R: p_0 = pre r_0 formed here from r0 / pre (FRow::p's rounded products), not read
-template <typename T, int L, bool P0R, bool NT = false>
+template <typename T, int L, bool P0R>
 __global__ __launch_bounds__(kBlock) void iw_update_all(Args<T> a, T* __restrict__ O, T* __restrict__ A,
                                                         const T* __restrict__ pall, long long pstride,
                                                         const double* __restrict__ sc, int sc0,
@@ -2075,14 +2052,9 @@ __global__ __launch_bounds__(kBlock) void iw_update_all(Args<T> a, T* __restrict
         T qt[L];
 #pragma unroll
         for (int i = P0R ? 1 : 0; i < L; ++i) {
-            if constexpr (NT) {   // streaming: every p element is read once
-                const T* pi = pall + i * pstride;
-                q[i] = Vec2<T>{ld_v<true>(pi + 2 * k), ld_v<true>(pi + 2 * k + 1)};
-                qt[i] = ld_v<true>(pi + 2 * N + k);
-            } else {
-                q[i] = reinterpret_cast<const Vec2<T>*>(pall + i * pstride)[k];
-                qt[i] = pall[i * pstride + 2 * N + k];
-            }
+            const T* pi = pall + i * pstride;   // streaming loads: every p element is read once
+            q[i] = Vec2<T>{ld_v<true>(pi + 2 * k), ld_v<true>(pi + 2 * k + 1)};
+            qt[i] = ld_v<true>(pi + 2 * N + k);
         }
         if constexpr (P0R) {
             const T w0 = pre_offset(a, f);
@@ -2115,11 +2087,8 @@ __global__ __launch_bounds__(kBlock) void iw_update_all(Args<T> a, T* __restrict
 // when the pairs are aligned (N % 4 == 0, even row starts, 16-B aligned arrays).
 template <typename T>
 using vec4_t = T __attribute__((ext_vector_type(4)));
-#ifndef IW_UPD_WAVES
-#define IW_UPD_WAVES 1   // A/B builds (tools/ab_build.sh): the minimum waves per SIMD iw_update_all2 is held to
-#endif
-template <typename T, int L, bool P0R, bool NT = false>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(IW_UPD_WAVES))) void iw_update_all2(Args<T> a, T* __restrict__ O, T* __restrict__ A,
+template <typename T, int L, bool P0R>
+__global__ __launch_bounds__(kBlock) void iw_update_all2(Args<T> a, T* __restrict__ O, T* __restrict__ A,
                                                          const T* __restrict__ pall, long long pstride,
                                                          const double* __restrict__ sc, int sc0,
                                                          const T* __restrict__ r0, const T* __restrict__ pre) {
@@ -2139,8 +2108,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(IW_UPD_W
 #pragma unroll
         for (int i = P0R ? 1 : 0; i < L; ++i) {
             const T* pi = pall + i * pstride;
-            q[i] = ld_v<NT>(reinterpret_cast<const vec4_t<T>*>(pi + 2 * k));
-            qt[i] = ld_v<NT>(reinterpret_cast<const vec2_t<T>*>(pi + 2 * N + k));
+            q[i] = ld_v<true>(reinterpret_cast<const vec4_t<T>*>(pi + 2 * k));   // streaming, as iw_update_all
+            qt[i] = ld_v<true>(reinterpret_cast<const vec2_t<T>*>(pi + 2 * N + k));
         }
         if constexpr (P0R) {   // iw_update_all's p_0 per pixel: the same rounded products
             const vec4_t<T> r = *reinterpret_cast<const vec4_t<T>*>(r0 + 2 * k);
@@ -2336,15 +2305,8 @@ public:
         bind(params, false);
         exchange_unknowns();
         const int L = std::max(0, sp_.lIterations);
-        red_.ensure(std::max({stencil_blocks(), fused_blocks(), side_blocks(), fused_side_blocks(), cost_side_blocks(), 2048}), 4,
+        red_.ensure(std::max({stencil_blocks(), fused_blocks(), fused_side_blocks(), kUpdBlocks}), 4,
                     kScBase + iw::kSlots * (L + 2));
-        if (print_addr_) {   // OPT_AMD_PRINT_ADDR=1: placement of every stream (HBM channel study)
-            print_addr_ = false;
-            fprintf(stderr, "[opt_amd] addr r=%p r1=%p p0=%p p1=%p Ap=%p Ap1=%p delta=%p pre=%p flags=%p "
-                    "O=%p A=%p U=%p C=%p M=%p\n", (void*)r_, (void*)r1_, (void*)p0_, (void*)p1_, (void*)Ap_,
-                    (void*)Ap1_, (void*)delta_, (void*)pre_, (void*)flags_, (void*)cur_O_, (void*)cur_A_,
-                    (void*)cur_U_, (void*)cur_C_, (void*)cur_M_);
-        }
         T* pcur = p0_;
         T* pprev = p1_;
         // PCGInit1 (r, pre, flags, rz[0]) from the arrays bound at THIS Step, as the
@@ -2413,8 +2375,8 @@ public:
         // interior row blocks of the next apply (halo_mark / halo_begin / halo_join)
         // (the last row block / chunk must hold >= 2 rows: only the first and last read halo rows)
         const bool split = distributed() && overlap_ && comm_->concurrent_halo() &&
-                           (pcg_side_ && apfree ? side_chunks() >= 3 && (dom_.y_hi - dom_.y_lo) - (side_chunks() - 1) * rows_ >= 2
-                                                : nrowblocks_ >= 3 && (dom_.y_hi - dom_.y_lo) - (nrowblocks_ - 1) * 4 * rows_ >= 2);
+                           (apfree ? side_chunks() >= 3 && (dom_.y_hi - dom_.y_lo) - (side_chunks() - 1) * rows_ >= 2
+                                   : nrowblocks_ >= 3 && (dom_.y_hi - dom_.y_lo) - (nrowblocks_ - 1) * 4 * rows_ >= 2);
         if (res) {
             // p_i in pb[i % 3] (deferred delta) or pb[i % 2]
             auto pbuf = [&](int i) { return allp ? pall_ + (size_t)i * 3 * dom_.npix_mem() : pb[defer ? i % 3 : i % 2]; };
@@ -2616,39 +2578,25 @@ public:
     }
 
 private:
-    // Measurement / A-B knobs, read once when the plan is created (never inside a Step):
-    // OPT_AMD_ROWS rows per wave (0: iw::rows_for), OPT_AMD_STAGGER the vectors' placement,
-    // and the separate-pass forms the tests compare bitwise with the fused loop
-    // (OPT_AMD_IW_FUSED_INIT / _FUSED_RES / _DEFER = 0).
+    // Knobs, read once when the plan is created (never inside a Step): OPT_AMD_ROWS rows per
+    // wave (0: iw::rows_for), and the forms the tests compare bitwise with the default loop or
+    // that the plan itself falls back to: the separate passes (OPT_AMD_IW_FUSED_INIT /
+    // _FUSED_RES = 0), the stored-Ap pass (_APFREE = 0), the delta forms (_DEFER, _ALLP,
+    // _ALLP_LIMIT_MB, _UPD_PAIRS), one row per trip (_PCG_U2 = 0), the stored angle
+    // preconditioner (_PCG_PRC = 0), the Mask cost (_COST_FLAGS = 0), forward-only kernels
+    // (_MALL_REV = 0), the record layout (_REC = 1; test_rec_layout_is_bitwise_the_image_layout).
     void read_knobs() {
         const int rw = env_int("OPT_AMD_ROWS", 0);
         if (rw > 0) { rows_ = rw; rows_auto_ = false; }
-        stagger_ = env_int("OPT_AMD_STAGGER", kStagger) & ~255LL;
-        print_addr_ = env_int("OPT_AMD_PRINT_ADDR", 0) != 0;
         fused_init_ = env_int("OPT_AMD_IW_FUSED_INIT", 1) != 0;
         fused_res_ = env_int("OPT_AMD_IW_FUSED_RES", 1) != 0;
         defer_ = env_int("OPT_AMD_IW_DEFER", 1) != 0;
-        side_ = env_int("OPT_AMD_IW_SIDE", 0) != 0;
         apfree_ = env_int("OPT_AMD_IW_APFREE", 1) != 0;
         rec_on_ = env_int("OPT_AMD_IW_REC", 0) != 0;
-        cost60_ = env_int("OPT_AMD_IW_COST60", 1) != 0;
-        cost_rows_ = (int)env_int("OPT_AMD_IW_COST_ROWS", 0);
         allp_ = env_int("OPT_AMD_IW_ALLP", 1) != 0;
-        upd_nt_ = env_int("OPT_AMD_IW_UPD_NT", 1) != 0;
-        upd_blocks_ = std::max(1, env_int("OPT_AMD_IW_UPD_BLOCKS", 2048));
-        pcg_nt_ = env_int("OPT_AMD_IW_PCG_NT", 0) != 0;
-        pcg_u2_ = env_int("OPT_AMD_IW_PCG_U2", 1);
-        slab_rows_ = env_int("OPT_AMD_IW_SLAB_ROWS", 1) != 0;
-        // iw_jtf_apply's 60-column strips store 240-B row segments that share cache lines
-        // with the neighbouring strips: plain stores (merged in the L2) measured 217-220 us
-        // against 233-245 with streaming ones (round 5, same box, interleaved)
-        jtf_nt_ = env_int("OPT_AMD_IW_JTF_NT", 0) != 0;
+        pcg_u2_ = env_int("OPT_AMD_IW_PCG_U2", 1) != 0;
         pall_limit_mb_ = env_int("OPT_AMD_IW_ALLP_LIMIT_MB", -1);
-        pcg_side_ = env_int("OPT_AMD_IW_PCG_SIDE", 1) != 0;
-        jtf_side_ = env_int("OPT_AMD_IW_JTF_SIDE", 0) != 0;
-        cost_side_ = env_int("OPT_AMD_IW_COST_SIDE", 0) != 0;
         upd_pairs_ = env_int("OPT_AMD_IW_UPD_PAIRS", 1) != 0;
-        pcg_alt_ = env_int("OPT_AMD_IW_PCG_ALT", 0) != 0;
         pcg_prc_ = env_int("OPT_AMD_IW_PCG_PRC", 1) != 0;
         cost_flags_ = env_int("OPT_AMD_IW_COST_FLAGS", 1) != 0;
         mall_rev_ = env_int("OPT_AMD_IW_MALL_REV", 1) != 0;
@@ -2656,27 +2604,26 @@ private:
     // A zeroed plan vector with kSlack spare bytes: place() may move each vector's base
     // within them between Steps (every vector is rewritten before it is read in a Step).
     static constexpr size_t kSlack = 1 << 20;
-    // default stagger: 9 pages. On one plan (same physical pages) staggers of 0 .. 128 KiB
-    // moved the 4096^2 GN step by 1-2.5 %, 0 the slowest and 36 KiB among the fastest on
-    // three plans (tools/ab_knobs.py)
-    static constexpr long long kStagger = 36864;
+    // Vector k starts (k kStagger) mod kSlack bytes into its allocation: 9 pages. On one plan
+    // (same physical pages) staggers of 0 .. 128 KiB moved the 4096^2 GN step by 1-2.5 %, 0 the
+    // slowest and 36 KiB among the fastest on three plans
+    static constexpr size_t kStagger = 36864;
+    static constexpr int kUpdBlocks = 2048;   // iw_update_all's grid cap (grid-stride beyond)
     void* vec_alloc(size_t bytes) {
         char* p = (char*)dmalloc(bytes + kSlack);
         raw_.push_back(p);
         OPT_HIP_CHECK(hipMemset(p, 0, bytes + kSlack));
         return p;
     }
-    // OPT_AMD_STAGGER=S: vector k starts (k S) mod kSlack bytes into its allocation (HBM
-    // placement study: the step time moves by up to ~8% with where the streams land)
     void place() {
         T** vs[] = {&r_, &p0_, &p1_, &Ap_, &delta_, &r1_, &Ap1_, &pre_, &p2_};
         if (raw_.size() < 10) return;
-        for (int k = 0; k < 8; ++k) *vs[k] = (T*)(raw_[k] + ((size_t)stagger_ * k) % kSlack);
-        flags_ = (uint8_t*)(raw_[8] + ((size_t)stagger_ * 8) % kSlack);
-        p2_ = (T*)(raw_[9] + ((size_t)stagger_ * 9) % kSlack);
+        for (int k = 0; k < 8; ++k) *vs[k] = (T*)(raw_[k] + (kStagger * k) % kSlack);
+        flags_ = (uint8_t*)(raw_[8] + (kStagger * 8) % kSlack);
+        p2_ = (T*)(raw_[9] + (kStagger * 9) % kSlack);
         if (recl_ && raw_.size() >= 14) {
-            for (int k = 0; k < 3; ++k) rec_[k] = (T*)(raw_[10 + k] + ((size_t)stagger_ * (10 + k)) % kSlack);
-            srec_ = (T*)(raw_[13] + ((size_t)stagger_ * 13) % kSlack);
+            for (int k = 0; k < 3; ++k) rec_[k] = (T*)(raw_[10 + k] + (kStagger * (10 + k)) % kSlack);
+            srec_ = (T*)(raw_[13] + (kStagger * 13) % kSlack);
         }
     }
     void allocate() {
@@ -2701,7 +2648,7 @@ private:
             rows_ = iw::rows_for(nstrips_, dom_.y_hi - dom_.y_lo);
             // a proper row slab (set_decomposition over part of the image; a one-rank
             // "split" of the whole image keeps the single-domain tiling, bitwise that path)
-            if (rows_ <= 16 && comm_ && slab_rows_ && (dom_.y_lo > 0 || dom_.y_hi < dom_.H)) {
+            if (rows_ <= 16 && comm_ && (dom_.y_lo > 0 || dom_.y_hi < dom_.H)) {
                 int dev = 0, cu = 0;
                 OPT_HIP_CHECK(hipGetDevice(&dev));
                 OPT_HIP_CHECK(hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev));
@@ -2710,8 +2657,7 @@ private:
             }
         }
         nrowblocks_ = (dom_.y_hi - dom_.y_lo + rows_ * 4 - 1) / (rows_ * 4);
-        red_.ensure(std::max({stencil_blocks(), fused_blocks(), cost_blocks(), cost_side_blocks(), fused_side_blocks(), 2048}),
-                    1, 64);
+        red_.ensure(std::max({stencil_blocks(), fused_blocks(), fused_side_blocks(), kUpdBlocks}), 1, 64);
         if (opts_.host_buffers) {
             dO_ = (T*)dmalloc(sizeof(T) * 2 * N);
             dA_ = (T*)dmalloc(sizeof(T) * N);
@@ -2724,8 +2670,7 @@ private:
     void launch_update_all_k(int L, bool p0r) {
         if constexpr (K <= iw::kAllPMax) {
             if (L != K) { launch_update_all_k<K + 1>(L, p0r); return; }
-            auto k = upd_nt_ ? (p0r ? iw::iw_update_all<T, K, true, true> : iw::iw_update_all<T, K, false, true>)
-                             : (p0r ? iw::iw_update_all<T, K, true> : iw::iw_update_all<T, K, false>);
+            auto k = p0r ? iw::iw_update_all<T, K, true> : iw::iw_update_all<T, K, false>;
             // pixel pairs when every pair is aligned (iw_update_all2)
             const long long Np = dom_.npix_mem(), b = dom_.off(0, dom_.y_lo), e = dom_.off(0, dom_.y_hi);
             auto al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
@@ -2736,10 +2681,9 @@ private:
             iw::Args<T> ua = args();
             ua.rev = mall_rev_ && !((L - 1) & 1) ? 1 : 0;
             if (pairs) {
-                auto k2 = upd_nt_ ? (p0r ? iw::iw_update_all2<T, K, true, true> : iw::iw_update_all2<T, K, false, true>)
-                                  : (p0r ? iw::iw_update_all2<T, K, true> : iw::iw_update_all2<T, K, false>);
+                auto k2 = p0r ? iw::iw_update_all2<T, K, true> : iw::iw_update_all2<T, K, false>;
                 const long long need = ((e - b) / 2 + kBlock - 1) / kBlock;
-                const int grid = (int)std::max(1LL, std::min<long long>(need, upd_blocks_));
+                const int grid = (int)std::max(1LL, std::min<long long>(need, kUpdBlocks));
                 hipLaunchKernelGGL(k2, dim3(grid), dim3(kBlock), 0, stream_, ua, cur_O_, cur_A_,
                                    (const T*)pall_, 3 * Np, (const double*)red_.scalars, rz(0), (const T*)r_,
                                    (const T*)pre_);
@@ -2747,7 +2691,7 @@ private:
                 return;
             }
             const long long need = (dom_.npix_mem() + kBlock - 1) / kBlock;
-            const int grid = (int)std::max(1LL, std::min<long long>(need, upd_blocks_));
+            const int grid = (int)std::max(1LL, std::min<long long>(need, kUpdBlocks));
             hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), 0, stream_, ua, cur_O_, cur_A_,
                                (const T*)pall_, 3 * dom_.npix_mem(), (const double*)red_.scalars, rz(0),
                                (const T*)r_, (const T*)pre_);
@@ -2836,10 +2780,6 @@ private:
     int pap(int i) const { return rz(i) + 1; }
 
     int stencil_blocks() const { return nstrips_ * nrowblocks_; }
-    // tiles of the side-by-side geometry (Args::side): groups of 4 strips x row chunks
-    int side_blocks() const {
-        return (nstrips_ + kBlock / kWave - 1) / (kBlock / kWave) * ((dom_.y_hi - dom_.y_lo + rows_ - 1) / rows_);
-    }
     // tiles of iw_jtf_apply: 60-column strips
     int fused_strips() const { return (dom_.W + iw::kFStrip - 1) / iw::kFStrip; }
     // the same with side-by-side waves (Args::side): groups of 4 strips x row chunks of rows_
@@ -2848,17 +2788,6 @@ private:
         return (fused_strips() + kBlock / kWave - 1) / (kBlock / kWave) * side_chunks();
     }
     int fused_blocks() const { return fused_strips() * nrowblocks_; }
-    // iw_cost60's rows per wave (OPT_AMD_IW_COST_ROWS; 0: the plan's rows, 32 at 4096^2 —
-    // 16 / 24 / 48 / 64 ran 138-146 us against 132-135, tools/r05_cost_rows_ab.sh; held to
-    // 64 VGPRs for 8 waves per SIMD instead of 6 it spilled and ran 141-142)
-    int cost_rows() const { return cost_rows_ > 0 ? cost_rows_ : rows_; }
-    int cost_side_blocks() const {
-        return (fused_strips() + kBlock / kWave - 1) / (kBlock / kWave) *
-               ((dom_.y_hi - dom_.y_lo + cost_rows() - 1) / cost_rows());
-    }
-    int cost_blocks() const {
-        return fused_strips() * ((dom_.y_hi - dom_.y_lo + cost_rows() * 4 - 1) / (cost_rows() * 4));
-    }
 
     iw::Args<T> args() const {
         iw::Args<T> a;
@@ -2870,7 +2799,6 @@ private:
         a.nstrips = nstrips_; a.nrowblocks = nrowblocks_; a.rows = rows_;
         a.tb0 = 0; a.tn0 = nstrips_ * nrowblocks_; a.tb1 = 0;
         a.side = 0;
-        a.alt = 0;
         a.rev = 0;
         a.S = srec_;
         // same float expression the reference's evalJTF + guardedInvert evaluate
@@ -2948,21 +2876,20 @@ private:
     void launch_jtf_apply(T* pout, bool no_ap, bool rec = false) {
         iw::Args<T> a = args();
         a.nstrips = fused_strips();
-        a.side = jtf_side_ ? 1 : 0;
-        const int nb = jtf_side_ ? fused_side_blocks() : fused_blocks();
+        const int nb = fused_blocks();
         a.tb0 = 0; a.tn0 = nb; a.tb1 = 0;   // every tile (geom_fused)
         if (rec) {
             if (!no_ap || (pout && pout != rec_[0])) throw std::logic_error("iw_jtf_apply<REC>: record 0 only, no Ap");
-            launch_timed("iw_jtf_apply", jtf_nt_ ? iw::iw_jtf_apply<T, 2, true> : iw::iw_jtf_apply<T, 0, true>, nb, a,
-                         rec_[0], (T*)nullptr, pout, (T*)nullptr, red_.slot(nb, rz(0)));
+            launch_timed("iw_jtf_apply", iw::iw_jtf_apply<T, true>, nb, a, rec_[0], (T*)nullptr, pout, (T*)nullptr,
+                         red_.slot(nb, rz(0)));
             return;
         }
-        launch_timed("iw_jtf_apply", jtf_nt_ ? iw::iw_jtf_apply<T, 2> : iw::iw_jtf_apply<T, 0>, nb, a, r_, pre_, pout,
+        launch_timed("iw_jtf_apply", iw::iw_jtf_apply<T>, nb, a, r_, pre_, pout,
                      no_ap ? nullptr : Ap_, red_.slot(nb, rz(0)));
     }
     // PCG iteration i >= 1 without a stored Ap (iw_pcg): reads r_{i-1} and p_{i-1}, writes
     // r_i (unless last) and p_i; the deferred delta and P0 exactly as launch_apply_res
-    // part 0: every row block; 1: the interior row blocks [1, nrb - 1); 2: the first and last
+    // part 0: every row chunk; 1: the interior row chunks [1, nch - 1); 2: the first and last
     // (the only ones that read halo rows: a wave reads rows y0 - 2 .. y1 + 1)
     // REC: pin / pout / pin2 are the records of iterations i-1, i, i-2 (r and p together)
     // nodelta (allp): no delta term in any pass (iw_update_all forms delta)
@@ -2974,73 +2901,49 @@ private:
         iw::Args<T> a = args();
         const int fs = fused_strips();
         a.nstrips = fs;
-        const int nb = fused_blocks();   // the reduction slot spans every tile
+        // side-by-side waves (Args::side): tile = row chunk x group of 4 strips
+        const int ng = (fs + kBlock / kWave - 1) / (kBlock / kWave), nch = side_chunks();
+        const int nb = ng * nch;   // the reduction slot spans every tile
+        a.side = 1;
         a.tb0 = 0; a.tn0 = nb; a.tb1 = 0;
         int grid = nb;
-        int nbr = nb;
-        a.alt = pcg_alt_ ? 1 : 0;
-        a.rev = mall_rev_ && (i & 1) ? 1 : 0;   // pass i after a forward iw_jtf_apply: odd passes backward
-        // the angle preconditioner recomputed (iw_pcg PRC): the mirrored walk sums its four
-        // edge terms in another order, so not with alt
-        const bool prc = pcg_prc_ && !pcg_alt_ && !rec;
-        if (pcg_side_) {   // side-by-side waves (Args::side): tile = row chunk x group of 4 strips
-            const int ng = (fs + kBlock / kWave - 1) / (kBlock / kWave), nch = side_chunks();
-            a.side = 1;
-            nbr = grid = a.tn0 = ng * nch;
-            if (part == 1) {
-                a.tb0 = ng; a.tn0 = ng * (nch - 2);
-                grid = a.tn0;
-            } else if (part == 2) {
-                a.tb0 = 0; a.tn0 = ng; a.tb1 = ng * (nch - 1);
-                grid = 2 * ng;
-            }
-        } else if (part == 1) {
-            a.tb0 = fs; a.tn0 = fs * (nrowblocks_ - 2);
+        if (part == 1) {
+            a.tb0 = ng; a.tn0 = ng * (nch - 2);
             grid = a.tn0;
         } else if (part == 2) {
-            a.tb0 = 0; a.tn0 = fs; a.tb1 = fs * (nrowblocks_ - 1);
-            grid = 2 * fs;
+            a.tb0 = 0; a.tn0 = ng; a.tb1 = ng * (nch - 1);
+            grid = 2 * ng;
         }
-        const ReduceSlot rs = red_.slot(nbr, rz(i));
+        a.rev = mall_rev_ && (i & 1) ? 1 : 0;   // pass i after a forward iw_jtf_apply: odd passes backward
+        const ReduceSlot rs = red_.slot(nb, rz(i));
         auto go = [&](auto kern) {
             launch_timed("iw_pcg", kern, grid, a, pin, rin, (const T*)pre_, pout, rout, delta_, red_.scalars,
                          rz(i - 1), base_scale, rs, pin2);
         };
-        auto pick = [&](auto nt, auto u2, auto pf2, auto dp) {
-            constexpr bool SNT = decltype(nt)::value, U2 = decltype(u2)::value, PF2 = decltype(pf2)::value,
-                           DP = decltype(dp)::value;
+        auto pick = [&](auto u2, auto dp) {
+            constexpr bool U2 = decltype(u2)::value, DP = decltype(dp)::value;
             if (nodelta) {
-                if constexpr (!DP && !PF2 && !SNT) {
-                    if (prc && !(i == 1 && p0)) {
-                        go(iw::iw_pcg<T, 0, 0, false, SNT, U2, PF2, DP, true>);
-                        return;
-                    }
-                }
-                if (i == 1 && p0) go(iw::iw_pcg<T, 0, 0, true, SNT, U2, PF2, DP>);
-                else go(iw::iw_pcg<T, 0, 0, false, SNT, U2, PF2, DP>);
+                if (i == 1 && p0) go(iw::iw_pcg<T, 0, 0, true, U2, DP>);
+                else if (pcg_prc_ && !DP) go(iw::iw_pcg<T, 0, 0, false, U2, false, true>);   // the angle pre recomputed (PRC)
+                else go(iw::iw_pcg<T, 0, 0, false, U2, DP>);
             } else if (pin2 || (defer_ && i == 1)) {
-                if (i == 1 && p0) go(iw::iw_pcg<T, 0, 0, true, SNT, U2, PF2, DP>);
-                else if (i % 2 == 1) go(iw::iw_pcg<T, 0, 0, false, SNT, U2, PF2, DP>);
-                else if (i == 2 && p0) go(iw::iw_pcg<T, 1, 1, true, SNT, U2, PF2, DP>);
-                else if (i == 2) go(iw::iw_pcg<T, 1, 1, false, SNT, U2, PF2, DP>);
-                else go(iw::iw_pcg<T, 2, 1, false, SNT, U2, PF2, DP>);
-            } else if (i == 1 && p0) go(iw::iw_pcg<T, 1, 0, true, SNT, U2, PF2, DP>);
-            else if (i == 1) go(iw::iw_pcg<T, 1, 0, false, SNT, U2, PF2, DP>);
-            else go(iw::iw_pcg<T, 2, 0, false, SNT, U2, PF2, DP>);
+                if (i == 1 && p0) go(iw::iw_pcg<T, 0, 0, true, U2, DP>);
+                else if (i % 2 == 1) go(iw::iw_pcg<T, 0, 0, false, U2, DP>);
+                else if (i == 2 && p0) go(iw::iw_pcg<T, 1, 1, true, U2, DP>);
+                else if (i == 2) go(iw::iw_pcg<T, 1, 1, false, U2, DP>);
+                else go(iw::iw_pcg<T, 2, 1, false, U2, DP>);
+            } else if (i == 1 && p0) go(iw::iw_pcg<T, 1, 0, true, U2, DP>);
+            else if (i == 1) go(iw::iw_pcg<T, 1, 0, false, U2, DP>);
+            else go(iw::iw_pcg<T, 2, 0, false, U2, DP>);
         };
-        using F = std::false_type;
-        using Tt = std::true_type;
         // row pairs only on waves of >= 16 rows: the 8-row waves of a row slab spend the
         // pair loop's prologue on too few rows (8 slabs of 4096 x 512 on one GPU, GN step
         // 7.2-7.6 ms with pairs against 6.5-7.0 without)
-        const int u2 = rows_ >= 16 ? pcg_u2_ : 0;
-        if (rec) {
-            if (u2 == 2) pick(F{}, Tt{}, Tt{}, Tt{});
-            else pick(F{}, F{}, F{}, Tt{});
-        } else if (u2 == 2) pick(F{}, Tt{}, Tt{}, F{});
-        else if (u2) pick(F{}, Tt{}, F{}, F{});
-        else if (pcg_nt_) pick(Tt{}, F{}, F{}, F{});
-        else pick(F{}, F{}, F{}, F{});
+        using F = std::false_type;
+        using Tt = std::true_type;
+        if (rec) pick(F{}, Tt{});   // the record layout walks one row per trip
+        else if (rows_ >= 16 && pcg_u2_) pick(Tt{}, F{});
+        else pick(F{}, F{});
     }
     // part 0: every row block; 1: the interior row blocks [1, nrb - 1); 2: the first and
     // last row blocks (the only ones whose stencil reads halo rows)
@@ -3091,10 +2994,8 @@ private:
         T* Apout = last ? nullptr : ab[i & 1];
         const double base_scale = (i == 1 && !spec_.use_preconditioner) ? 4.0 : 1.0;
         iw::Args<T> a = args();
-        const bool side = side_ && part == 0;
-        const int nb = side ? side_blocks() : stencil_blocks();   // the reduction slot spans every tile
+        const int nb = stencil_blocks();   // the reduction slot spans every tile
         int grid = nb;
-        if (side) { a.side = 1; a.tn0 = nb; }
         if (part == 1) {
             a.tb0 = nstrips_; a.tn0 = nstrips_ * (nrowblocks_ - 2);
             grid = a.tn0;
@@ -3129,16 +3030,10 @@ private:
     // fl: the flag byte of this Step's iw_jtf_apply / iw_jtf is valid for the bound arrays
     // (the cost at the end of a Step; not Init's or OptAMD_EvalCost's)
     void launch_cost(int sc_out, bool fl = false, bool rev = false) {
-        if (offsets32_ && cost60_) {
+        if (offsets32_) {
             iw::Args<T> a = args();
             a.nstrips = fused_strips();
-            a.rows = cost_rows();
-            a.nrowblocks = (dom_.y_hi - dom_.y_lo + a.rows * 4 - 1) / (a.rows * 4);
-            int nb = a.nstrips * a.nrowblocks;
-            if (cost_side_) {   // side-by-side waves (Args::side)
-                a.side = 1;
-                nb = cost_side_blocks();
-            }
+            const int nb = fused_blocks();
             a.tb0 = 0; a.tn0 = nb; a.tb1 = 0;
             a.rev = rev ? 1 : 0;
             if (fl && cost_flags_)
@@ -3164,58 +3059,33 @@ private:
     T *r1_ = nullptr, *Ap1_ = nullptr;   // iw_apply_res ping-pongs r and Ap (neighbours read the old ones)
     T* p2_ = nullptr;                    // p_i in {p0_, p1_, p2_}[i % 3] with the deferred delta
     std::vector<char*> raw_;             // the plan vectors' allocations (vec_alloc)
-    long long stagger_ = kStagger;
-    bool print_addr_ = false;
     uint8_t* flags_ = nullptr;
     bool fused_init_ = true;            // OPT_AMD_IW_FUSED_INIT=0: iw_jtf, then iw_apply<1,0>
     bool fused_res_ = true;             // OPT_AMD_IW_FUSED_RES=0: iw_apply<2> + iw_residual per iteration
     bool defer_ = true;                 // OPT_AMD_IW_DEFER=0: iw_apply_res updates delta in every iteration
-    bool side_ = false;                 // OPT_AMD_IW_SIDE=1: iw_apply_res with side-by-side waves (Args::side)
     bool apfree_ = true;                // OPT_AMD_IW_APFREE=0: iw_apply_res (stored Ap) instead of iw_pcg
     // OPT_AMD_IW_REC=1: the fused loop's vectors as records (Args::S). Measured slower (round 5,
     // interleaved A/B, 4096^2 fp32 GN step 3.99 against 3.75 ms: iw_jtf_apply writes 41 B/px
     // instead of 17, 318 against 218 us; iw_pcg 354 against 347 us — the pass is bound by its
     // VALU work and latency, not by the strip edges' partial lines)
     bool rec_on_ = false;
-    // OPT_AMD_IW_COST60=0: the cost on 64-column strips with edge loads (iw_cost; 147 against
-    // 141 us at 4096^2 fp32). A flat one-pixel-per-thread form with direct neighbour loads
-    // measured 297 us, a bitwise copy of sincosf's small-argument path no change (the device
-    // library already branches around its large-argument reduction): the strip kernels are
-    // bound by their VALU work and load latency, not by the sine
-    bool cost60_ = true;
     // OPT_AMD_IW_ALLP=0: the deferred delta (pairs folded by the even passes) instead of every
     // p_i kept for iw_update_all
     bool allp_ = true;
-    // OPT_AMD_IW_UPD_NT=0: iw_update_all with plain loads of the p vectors (streaming: update
-    // 510-518 -> 474 us, the following cost 116 -> 135 us, GN step 3.39-3.40 -> 3.34-3.37 ms)
-    bool upd_nt_ = true;
-    int upd_blocks_ = 2048;             // OPT_AMD_IW_UPD_BLOCKS: iw_update_all's grid cap (grid-stride beyond)
     T* pall_ = nullptr;                 // allp: lIterations p vectors of 3 N, p_i = pall_ + 3 N i
     int pall_cap_ = 0;
     bool pall_warned_ = false;
     bool mall_rev_ = true;              // OPT_AMD_IW_MALL_REV=0: every kernel of the Step walks forward (Args::rev)
     bool cost_flags_ = true;            // OPT_AMD_IW_COST_FLAGS=0: the Step's cost reads Mask and every Constraint
     bool pcg_prc_ = true;               // OPT_AMD_IW_PCG_PRC=0: iw_pcg reads the stored angle preconditioner
-    bool pcg_alt_ = false;              // OPT_AMD_IW_PCG_ALT=1: iw_pcg's odd row chunks walk upward (Args::alt)
     bool upd_pairs_ = true;             // OPT_AMD_IW_UPD_PAIRS=0: iw_update_all one pixel per thread
-    // OPT_AMD_IW_PCG_SIDE (default 1): iw_pcg with side-by-side waves (Args::side) — the block's
-    // four waves walk the same rows of four adjacent 60-column strips (round 6: 270 -> 257 us
-    // per pass at 4096^2, same box interleaved); 0 the four waves stacked over one strip
-    bool pcg_side_ = true;
-    bool jtf_side_ = false;             // OPT_AMD_IW_JTF_SIDE=1: iw_jtf_apply side by side
-    bool cost_side_ = false;            // OPT_AMD_IW_COST_SIDE=1: iw_cost60 side by side
     long long pall_limit_mb_ = -1;      // OPT_AMD_IW_ALLP_LIMIT_MB: cap on the kept p vectors (tests the fallback)
     bool recl_ = false;                 // the plan holds the REC layout (rec_on_ and the fused loop's knobs)
     T* rec_[3] = {nullptr, nullptr, nullptr};   // REC: iteration i's record in rec_[i % 3] (i % 2 undeferred)
     T* srec_ = nullptr;                 // REC: the S record [u.x u.y angle pre_t], written by iw_jtf_apply
-    bool pcg_nt_ = false;               // OPT_AMD_IW_PCG_NT=1: iw_pcg with streaming stores
-    // OPT_AMD_IW_PCG_U2: 0 one row per loop trip, 1 (default since the kept-p loop: 275 ->
-    // 270 us per pass, GN step 3.35 -> 3.30 ms) two rows with the records swapping roles,
-    // 2 the same with two raw rows in flight
-    int pcg_u2_ = 1;
-    bool slab_rows_ = true;   // OPT_AMD_IW_SLAB_ROWS=0: row slabs keep rows_for's 16-row floor (iw::rows_one_round)
-    int cost_rows_ = 0;
-    bool jtf_nt_ = false;               // OPT_AMD_IW_JTF_NT=1: iw_jtf_apply with streaming stores
+    // OPT_AMD_IW_PCG_U2=0: iw_pcg walks one row per loop trip instead of two with the records
+    // swapping roles (the plan itself takes one row per trip on waves of < 16 rows, launch_pcg)
+    bool pcg_u2_ = true;
     bool offsets32_ = true;             // iw_apply_res's 32-bit byte offsets cover every plan vector
     int rows_ = 0, nstrips_ = 0, nrowblocks_ = 0;
     bool rows_auto_ = true;

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Round 6: one rank's slab (tools/slab_rank.py) for image_warping GN and shape_from_shading LM,
-# with the rows-per-wave / side / FUSE23 A/B: tools/r06_slab.sh <outdir> [iw|sfs|both]
+# with the rows-per-wave / FUSE23 A/B: tools/r06_slab.sh <outdir> [iw|sfs|both]
 # (VARIANTS=closing: the round-6 closing set)
 set -o pipefail
 O=gpurun_out/$1; mkdir -p $O; WHICH=${2:-both}
@@ -22,8 +22,6 @@ else
 run iw_rows_auto OPT_AMD_X=0
 run iw_rows16 OPT_AMD_ROWS=16
 run iw_rows24 OPT_AMD_ROWS=24
-run iw_rows_auto_noside OPT_AMD_IW_PCG_SIDE=0
-run iw_rows16_jtfside OPT_AMD_ROWS=16 OPT_AMD_IW_JTF_SIDE=1 OPT_AMD_IW_COST_SIDE=1
 fi
 fi
 if [ $WHICH != iw ]; then
