@@ -23,6 +23,14 @@ extern "C" {
 /* Total number of scalar unknowns of the plan (e.g. 3*W*H for image_warping). */
 long long OptAMD_PlanUnknownCount(Opt_Plan* plan);
 
+/* The unknown vector r, pre, p and Ap are laid out over: one contiguous block per unknown
+ * image, in problemparams order, channels interleaved. For each of the first maxImages
+ * images writes the block's first element, its element (pixel) count and its channels
+ * (any of the three arrays may be NULL); the blocks differ in length when the unknowns
+ * lie over several index spaces. Returns the number of unknown images, -1 on a null plan. */
+int OptAMD_PlanUnknownLayout(Opt_Plan* plan, int maxImages, long long* offset, long long* elements,
+                             int* channels);
+
 /* Energy family the problem was lowered to ("image_warping", "poisson_image_editing",
  * ...); writes a NUL-terminated name into buf. Returns the name length. */
 int OptAMD_PlanFamily(Opt_Plan* plan, char* buf, int buflen);

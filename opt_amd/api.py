@@ -53,6 +53,8 @@ _SIGNATURES = [
     ("Opt_ProblemStep", ctypes.c_int, [_VP, _VP, ctypes.POINTER(_VP)]),
     ("Opt_ProblemCurrentCost", ctypes.c_double, [_VP, _VP]),
     ("OptAMD_PlanUnknownCount", ctypes.c_longlong, [_VP]),
+    ("OptAMD_PlanUnknownLayout", ctypes.c_int, [_VP, ctypes.c_int, ctypes.POINTER(ctypes.c_longlong),
+                                                ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_int)]),
     ("OptAMD_PlanFamily", ctypes.c_int, [_VP, ctypes.c_char_p, ctypes.c_int]),
     ("OptAMD_ProblemFamily", ctypes.c_int, [_VP, ctypes.c_char_p, ctypes.c_int]),
     ("OptAMD_GenericSignature", ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int]),
@@ -250,6 +252,15 @@ class OptSolver:
     # ---- extensions (include/opt_amd.h) ----------------------------------------
     def unknown_count(self) -> int:
         return self.lib.OptAMD_PlanUnknownCount(self.plan)
+
+    def unknown_layout(self):
+        """(offsets, elements, channels) of the unknown images' blocks in r / pre / p / Ap
+        (OptAMD_PlanUnknownLayout); the blocks differ in length over several index spaces."""
+        off, n, ch = (ctypes.c_longlong * 4)(), (ctypes.c_longlong * 4)(), (ctypes.c_int * 4)()
+        k = self.lib.OptAMD_PlanUnknownLayout(self.plan, 4, off, n, ch)
+        if k < 0:
+            raise OptError("OptAMD_PlanUnknownLayout failed")
+        return list(off)[:k], list(n)[:k], list(ch)[:k]
 
     def family(self) -> str:
         buf = ctypes.create_string_buffer(64)

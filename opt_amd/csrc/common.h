@@ -46,7 +46,8 @@ struct VecLayout {
     int nimg;
     int ch[4];
     long long off[5];
-    long long N;       // pixels in memory
+    long long N;       // flag bytes: pixels in memory (several index spaces: of all of them)
+    long long fbase[4]; // per image: first flag byte of its index space (0 with one space)
     // local element index -> pixel: channel counts 1..4 by shifts / a constant divide
     // (no 64-bit integer division in the flat PCG kernels)
     __host__ __device__ static long long div_ch(long long l, int c) {
@@ -63,7 +64,7 @@ struct VecLayout {
         while (k + 1 < nimg && e >= off[k + 1]) ++k;
         *img = k;
         *local = e - off[k];
-        return div_ch(*local, ch[k]);
+        return fbase[k] + div_ch(*local, ch[k]);
     }
     __host__ __device__ long long pix(long long e) const {
         int k;

@@ -96,7 +96,8 @@ struct GraphCache {
     int img = -1, width = 0;
     std::map<std::tuple<int, int, int>, int> ch;
 };
-const GraphCache* g_gcache = nullptr;
+// one per index space whose arrays the slot reads' transcendentals are of
+const std::map<int, GraphCache>* g_gcache = nullptr;
 // Slot reads (graph gathers) as uniform base + 32-bit byte offset (generate's off32): the
 // saddr form of global_load, one 32-bit multiply per neighbour instead of a 64-bit address
 // per gathered array
@@ -158,14 +159,19 @@ public:
         auto it = done_.find(id);
         if (it != done_.end()) return it->second;
         const Node n = P_.at(id);
+        const GraphCache* gc = nullptr;
         if (g_gcache && cacheable_slot(P_, n)) {
+            auto gi = g_gcache->find(M_.images[P_.at(n.a).i].space);
+            if (gi != g_gcache->end()) gc = &gi->second;
+        }
+        if (gc) {
             const Node c = P_.at(n.a);
-            auto ci = g_gcache->ch.find(std::make_tuple((int)n.op, c.i, c.ch));
-            if (ci != g_gcache->ch.end()) {
-                const int W = g_gcache->width, k = ci->second;
-                const std::string rec = "((const T*)a.img[" + std::to_string(g_gcache->img) + "]) + (long long)v" +
+            auto ci = gc->ch.find(std::make_tuple((int)n.op, c.i, c.ch));
+            if (ci != gc->ch.end()) {
+                const int W = gc->width, k = ci->second;
+                const std::string rec = "((const T*)a.img[" + std::to_string(gc->img) + "]) + (long long)v" +
                                         std::to_string(c.slot) + " * " + std::to_string(W);
-                const std::string rec32 = "opt_g32((const T*)a.img[" + std::to_string(g_gcache->img) + "], v" +
+                const std::string rec32 = "opt_g32((const T*)a.img[" + std::to_string(gc->img) + "], v" +
                                           std::to_string(c.slot) + ", " + std::to_string(W) + ", ";
                 std::string name;
                 // the slot's whole record once as 16-byte vectors (per-edge kernels: gen_cost
@@ -449,7 +455,8 @@ GenSource generate(GModel& m, bool dbl, bool off32) {
     o << "// generated by opt_amd's energy front end (gen/codegen.cpp)\n";
     o << "typedef " << (dbl ? "double" : "float") << " T;\n";
     o << "typedef T OptV4 __attribute__((ext_vector_type(4)));\n";
-    o << OPTAMD_STR(OPTAMD_GENARGS_BODY) << "\n";
+    o << "struct GenArgs { " << OPTAMD_STR(OPTAMD_GENARGS_FIELDS)
+      << (m.multi() ? " " OPTAMD_STR(OPTAMD_GENARGS_SPACES) : "") << " };\n";
     o << kReduceDevSrc << "\n";
     o << "#define OPT_COORDS const int W = a.dims[0], H = a.dims[1], D = a.dims[2]; (void)D;\n";
     o << "__device__ __forceinline__ void opt_sincos(float x, float* s, float* c) { sincosf(x, s, c); }\n"
@@ -536,13 +543,15 @@ GenSource generate(GModel& m, bool dbl, bool off32) {
     // is global row a.ymem0 (coordinates, bounds and Index(1) are global)
     // (32-bit unsigned divisions: the pixel index fits an int, as `li` assumes; a 64-bit
     // division is a ~100-instruction sequence per pixel)
-    const char* coords = nd == 2
-        ? "        const unsigned ul = (unsigned)lin, uq = ul / (unsigned)W;\n"
+    const char* coords2 =
+          "        const unsigned ul = (unsigned)lin, uq = ul / (unsigned)W;\n"
           "        const int x = (int)(ul - uq * (unsigned)W); const int y = (int)uq + a.ymem0; const int z = 0;\n"
-          "        const int li = (int)lin; (void)x; (void)y; (void)z; (void)li;\n"
-        : "        const unsigned ul = (unsigned)lin, uq = ul / (unsigned)W, uz = uq / (unsigned)H;\n"
+          "        const int li = (int)lin; (void)x; (void)y; (void)z; (void)li;\n";
+    const char* coords3 =
+          "        const unsigned ul = (unsigned)lin, uq = ul / (unsigned)W, uz = uq / (unsigned)H;\n"
           "        const int x = (int)(ul - uq * (unsigned)W); const int y = (int)(uq - uz * (unsigned)H); const int z = (int)uz;\n"
           "        const int li = (int)lin; (void)x; (void)y; (void)z; (void)li;\n";
+    const char* coords = nd == 2 ? coords2 : coords3;
 
     // centred instances per output (unknown image, channel)
     std::map<std::pair<int, int>, std::vector<std::pair<Instance, int>>> inst;   // -> (instance, support node)
@@ -558,24 +567,55 @@ GenSource generate(GModel& m, bool dbl, bool off32) {
     auto shifted = [&](int id, const int* s) { return P.shift(id, s); };
     const int zero3[3] = {0, 0, 0};
 
+    // Kernel loops over the elements of an index space. One space (every energy until
+    // bundle_adjustment.t / row_bias.t): the owned pixels of the unknowns' domain, a.dims.
+    // Several (mspace): one grid-stride loop per space inside the same kernel, W / H / D and
+    // the flag base fb taken from that space's GenArgs entries; such energies run the gather
+    // forms only (no strips, tiles, slabs or Jacobian dump).
+    const bool mspace = m.multi();
+    const std::vector<int> uspaces = mspace ? m.unknown_spaces() : std::vector<int>{0};
+    auto nd_of = [&](int sp) { return mspace ? (int)m.spaces[sp].size() : nd; };
+    auto coords_of = [&](int ndim) { return ndim == 2 ? coords2 : coords3; };
+    const std::string top_coords = mspace ? "" : "    OPT_COORDS\n";
+    auto open_space = [&](int sp) -> std::string {
+        if (mspace && (sp < 0 || sp >= (int)m.spaces.size())) {
+            fprintf(stderr, "[opt_amd] codegen: kernel loop over an unknown index space %d\n", sp);
+            abort();
+        }
+        if (!mspace)
+            return std::string("    for (long long lin = a.own_lo + (long long)blockIdx.x * 256 + threadIdx.x; lin < a.own_hi; lin += (long long)gridDim.x * 256) {\n") +
+                   coords_of(nd);
+        const std::string s = std::to_string(sp);
+        return "    {\n    const int W = a.sdims[" + s + "][0], H = a.sdims[" + s + "][1], D = a.sdims[" + s + "][2]; (void)H; (void)D;\n"
+               "    const long long fb = a.fbase[" + s + "]; (void)fb;\n"
+               "    for (long long lin = (long long)blockIdx.x * 256 + threadIdx.x; lin < a.snpix[" + s + "]; lin += (long long)gridDim.x * 256) {\n" +
+               coords_of(nd_of(sp));
+    };
+    const std::string close_space = mspace ? "    }\n    }\n" : "    }\n";
+    const std::string flag_lin = mspace ? "a.flags[fb + lin]" : "a.flags[lin]";
+    auto in_space = [&](int image, int sp) { return !mspace || m.images[image].space == sp; };
+
     // --------------------------------------------- gen_precompute_<k> (ComputedArrays)
     // One kernel per ComputedArray, launched in declaration order (a later one may read an
     // earlier one at an offset): the values and the non-constant gradient images
     // (createprecomputed, o.t:3131-3153).
     for (size_t k = 0; k < m.computed.size(); ++k) {
         const GComputed& c = m.computed[k];
+        const int csp = m.images[c.image].space;   // its kernel runs over its image's space
+        if (mspace && (csp < 0 || csp >= (int)m.spaces.size() || csp != c.space)) {
+            fprintf(stderr, "[opt_amd] codegen: computed array '%s' carries no index space\n", m.images[c.image].name.c_str());
+            abort();
+        }
         o << "extern \"C\" __global__ __launch_bounds__(256) void gen_precompute_" << k << "(GenArgs a) {\n"
-             "    OPT_COORDS\n"
-             "    for (long long lin = a.own_lo + (long long)blockIdx.x * 256 + threadIdx.x; lin < a.own_hi; lin += (long long)gridDim.x * 256) {\n"
-          << coords;
-        Body b(m, o, nd, uslot);
+          << top_coords << open_space(csp);
+        Body b(m, o, nd_of(csp), uslot);
         const int nch = (int)c.expr.size();
         for (int ch = 0; ch < nch; ++ch)
             b.line("((T*)a.img[" + std::to_string(c.image) + "])[lin * " + std::to_string(nch) + " + " + std::to_string(ch) +
                    "] = " + b.v(c.expr[ch]) + ";");
         for (const GGrad& g : c.grads)
             if (g.gimg >= 0) b.line("((T*)a.img[" + std::to_string(g.gimg) + "])[lin] = " + b.v(g.expr) + ";");
-        o << "    }\n}\n";
+        o << close_space << "}\n";
     }
     gs.n_precompute = (int)m.computed.size();
 
@@ -597,7 +637,7 @@ GenSource generate(GModel& m, bool dbl, bool off32) {
             multi |= offs.size() > 1;
         }
         std::vector<std::pair<std::tuple<int, int, int>, int>> want;   // key -> a node with offset 0 form
-        if (multi)
+        if (multi && !mspace)
             for (auto& r : m.residuals) {
                 if (r.graph >= 0) continue;
                 P.visit(r.expr, [&](int, const Node& n) {
@@ -675,7 +715,7 @@ GenSource generate(GModel& m, bool dbl, bool off32) {
                 pcache.at0.push_back(left ? cmp0(n.op, 0.0, c) : cmp0(n.op, c, 0.0));
             });
         };
-        if (on && uimg >= 0 && m.images.size() < 16 && nd == 2) {
+        if (on && uimg >= 0 && m.images.size() < 16 && nd == 2 && !mspace) {
             for (auto& r : m.residuals)
                 if (r.graph < 0) consider(r.expr);
             if (m.exclude >= 0) consider(m.exclude);
@@ -714,11 +754,15 @@ GenSource generate(GModel& m, bool dbl, bool off32) {
 
     // graph record cache (see g_gcache): transcendentals of slot reads of arrays on the
     // unknowns' domain, one record per vertex, filled by one more precompute kernel
-    GraphCache gcache;
-    {
+    // (several index spaces: one record image and kernel per unknown-carrying space)
+    std::map<int, GraphCache> gcaches;
+    for (int csp : uspaces) {
+        GraphCache gcache;
         const char* ev = getenv("OPT_AMD_GEN_GRAPH_CACHE");
         const bool on = !ev || atoi(ev) != 0;
-        const int uimg = unk.empty() ? -1 : unk[0];
+        int uimg = -1;
+        for (int k : unk)
+            if (uimg < 0 && in_space(k, csp)) uimg = k;
         std::vector<std::pair<std::tuple<int, int, int>, int>> want;
         if (on && uimg >= 0 && m.images.size() < 16)
             for (auto& r : m.residuals) {
@@ -740,16 +784,15 @@ GenSource generate(GModel& m, bool dbl, bool off32) {
             GImage ci;
             ci.name = "graph_cache";
             ci.dims = m.images[uimg].dims;
+            ci.space = m.images[uimg].space;
             ci.channels = width;
             ci.internal = ci.tvalued = true;
             m.images.push_back(ci);
             gcache.img = (int)m.images.size() - 1;
             gcache.width = width;
             o << "extern \"C\" __global__ __launch_bounds__(256) void gen_precompute_" << gs.n_precompute << "(GenArgs a) {\n"
-                 "    OPT_COORDS\n"
-                 "    for (long long lin = a.own_lo + (long long)blockIdx.x * 256 + threadIdx.x; lin < a.own_hi; lin += (long long)gridDim.x * 256) {\n"
-              << coords;
-            Body b(m, o, nd, uslot);
+              << top_coords << open_space(csp);
+            Body b(m, o, nd_of(csp), uslot);
             std::vector<std::string> val(width, "(T)0");
             for (size_t k = 0; k < want.size(); ++k) {
                 gcache.ch[want[k].first] = (int)k;
@@ -764,23 +807,26 @@ GenSource generate(GModel& m, bool dbl, bool off32) {
             } else {
                 for (int k = 0; k < width; ++k) b.line("(" + base + ")[" + std::to_string(k) + "] = " + val[k] + ";");
             }
-            o << "    }\n}\n";
+            o << close_space << "}\n";
             ++gs.n_precompute;
+            gcaches[m.images[uimg].space] = gcache;
         }
     }
-    g_gcache = gcache.img < 0 ? nullptr : &gcache;
+    g_gcache = gcaches.empty() ? nullptr : &gcaches;
 
     // ---------------------------------------------------------------- gen_jtf
     {
         o << "extern \"C\" __global__ __launch_bounds__(256) void gen_jtf(GenArgs a, T* __restrict__ r, T* __restrict__ diag) {\n"
-             "    OPT_COORDS\n"
-             "    for (long long lin = a.own_lo + (long long)blockIdx.x * 256 + threadIdx.x; lin < a.own_hi; lin += (long long)gridDim.x * 256) {\n"
-          << coords;
-        Body b(m, o, nd, uslot);
-        const std::string act = m.exclude >= 0 ? "(" + b.v(m.exclude) + " == (T)0)" : "true";
+          << top_coords;
+        for (int sp : uspaces) {
+        o << open_space(sp);
+        Body b(m, o, nd_of(sp), uslot);
+        const int excl = mspace ? m.exclude_of(sp) : m.exclude;
+        const std::string act = excl >= 0 ? "(" + b.v(excl) + " == (T)0)" : "true";
         b.line("const bool act = " + act + ";");
-        b.line("a.flags[lin] = act ? 1 : 0;");
+        b.line(flag_lin + " = act ? 1 : 0;");
         for (int k : unk) {
+            if (!in_space(k, sp)) continue;
             const GImage& im = m.images[k];
             for (int c = 0; c < im.channels; ++c) {
                 std::vector<std::string> F, Dg;
@@ -806,7 +852,9 @@ GenSource generate(GModel& m, bool dbl, bool off32) {
                 b.line("  r[" + e + "] = act ? -F : (T)0; diag[" + e + "] = Dg; }");
             }
         }
-        o << "    }\n}\n";
+        o << close_space;
+        }
+        o << "}\n";
     }
 
     // ------------------------------------------------------------ gen_apply_tiled
@@ -825,7 +873,7 @@ GenSource generate(GModel& m, bool dbl, bool off32) {
     int PX = 32, PY = 8, TX = 0, TY = 0, nf = 0;
     size_t lds = 0;
     bool tiled = false;
-    if (gs.has_centered && nd == 2) {
+    if (gs.has_centered && nd == 2 && !mspace) {
         for (size_t ri = 0; ri < m.residuals.size(); ++ri) {
             const GResidual& r = m.residuals[ri];
             if (r.graph >= 0 || r.unknowns.empty()) continue;
@@ -867,10 +915,11 @@ GenSource generate(GModel& m, bool dbl, bool off32) {
     // The gather form of the centred J^T J p at pixel `lin` (coordinates in scope). fused:
     // inside gen_apply_graph, the sum of output (k, c) goes to cacc<slot>_<c> (declared by
     // the caller) instead of Ap
-    auto centred_apply = [&](Body& b, bool fused) {
-        if (!fused) b.line("const bool act = (a.flags[lin] & 1) != 0;");
+    auto centred_apply = [&](Body& b, bool fused, int sp) {
+        if (!fused) b.line("const bool act = (" + flag_lin + " & 1) != 0;");
         std::map<std::string, std::string> jp;   // (residual, shift) -> J p of that instance
         for (int k : unk) {
+            if (!in_space(k, sp)) continue;
             const GImage& im = m.images[k];
             for (int c = 0; c < im.channels; ++c) {
                 std::vector<std::string> terms;
@@ -913,14 +962,15 @@ GenSource generate(GModel& m, bool dbl, bool off32) {
         o << "extern \"C\" __global__ __launch_bounds__(256) void gen_apply(GenArgs a, const T* __restrict__ p, T* __restrict__ Ap,\n"
              "        const T* __restrict__ dadd, const int* stop, ReduceSlot rs, int finish) {\n"
              "    if (stop && *stop) return;\n"
-             "    OPT_COORDS\n"
+          << top_coords <<
              "    T dot = 0;\n";
-        o << "    for (long long lin = a.own_lo + (long long)blockIdx.x * 256 + threadIdx.x; lin < a.own_hi; lin += (long long)gridDim.x * 256) {\n"
-              << coords;
-        Body b(m, o, nd, uslot);
-        centred_apply(b, false);
-        o << "    }\n"
-             "    if (finish) { double v[1] = {(double)dot}; block_reduce_publish<1>(v, rs, blockIdx.x); }\n}\n";
+        for (int sp : uspaces) {
+            o << open_space(sp);
+            Body b(m, o, nd_of(sp), uslot);
+            centred_apply(b, false, sp);
+            o << close_space;
+        }
+        o << "    if (finish) { double v[1] = {(double)dot}; block_reduce_publish<1>(v, rs, blockIdx.x); }\n}\n";
     }
 
     if (tiled) {
@@ -1486,6 +1536,7 @@ GenSource generate(GModel& m, bool dbl, bool off32) {
         std::vector<int> order;   // spec domains in order of first appearance
         for (auto& r : m.residuals)
             if (std::find(order.begin(), order.end(), r.graph) == order.end()) order.push_back(r.graph);
+        if (mspace) order.clear();   // no Jacobian dump over several index spaces (the plan refuses it)
         for (size_t si = 0; si < order.size(); ++si) {
             const int g = order[si];
             std::vector<const GResidual*> rs;
@@ -1554,16 +1605,21 @@ GenSource generate(GModel& m, bool dbl, bool off32) {
     // ------------------------------------------------------- cost (centres + edges)
     {
         o << "extern \"C\" __global__ __launch_bounds__(256) void gen_cost(GenArgs a, const T* __restrict__ delta, ReduceSlot rs) {\n"
-             "    OPT_COORDS\n"
+          << top_coords <<
              "    T acc = 0;\n";
-        if (gs.has_centered) {
-            o << "    for (long long lin = a.own_lo + (long long)blockIdx.x * 256 + threadIdx.x; lin < a.own_hi; lin += (long long)gridDim.x * 256) {\n"
-              << coords;
-            Body b(m, o, nd, uslot);
-            if (m.exclude >= 0) b.line("if (" + b.v(m.exclude) + " != (T)0) continue;");
+        for (int sp : uspaces) {
+            // the centred residuals of this space (one space: all of them)
+            auto here = [&](const GResidual& r) { return r.graph < 0 && (!mspace || r.space == sp); };
+            bool any = false;
+            for (auto& r : m.residuals) any |= here(r);
+            if (!any) continue;
+            o << open_space(sp);
+            Body b(m, o, nd_of(sp), uslot);
+            const int excl = mspace ? m.exclude_of(sp) : m.exclude;
+            if (excl >= 0) b.line("if (" + b.v(excl) + " != (T)0) continue;");
             std::string sum = "(T)0", msum = "(T)0";
             for (auto& r : m.residuals) {
-                if (r.graph >= 0) continue;
+                if (!here(r)) continue;
                 const std::string R = b.v(r.expr);
                 sum += " + " + R + " * " + R;
             }
@@ -1573,7 +1629,7 @@ GenSource generate(GModel& m, bool dbl, bool off32) {
                 int idx = 0;
                 std::string ms = "(T)0";
                 for (auto& r : m.residuals) {
-                    if (r.graph >= 0) continue;
+                    if (!here(r)) continue;
                     std::string e = b.v(r.expr);
                     for (int u : r.unknowns) {
                         const int gu = P.diff(r.expr, u);
@@ -1589,7 +1645,7 @@ GenSource generate(GModel& m, bool dbl, bool off32) {
             }
             b.line("}");
             b.line("acc += (T)0.5 * s;");
-            o << "    }\n";
+            o << close_space;
         }
         for (size_t g = 0; g < m.graphs.size(); ++g) {
             bool any = false;
@@ -1649,10 +1705,13 @@ GenSource generate(GModel& m, bool dbl, bool off32) {
     // the edges whose slot k is this vertex, ascending): no atomics, a fixed summation
     // order (bitwise reproducible), each edge evaluated once per incident slot. The same
     // kernel finishes the element (exclusion mask, LM diagonal, p.Ap).
-    auto graph_gather = [&](bool apply) {
+    // Several index spaces: the vertices of space sp gather through the slots that index sp
+    // (an unknown read at slot k lies over slot k's space, so only sp's unknowns accumulate);
+    // the other slots' vertices come from the gnb copies as before.
+    auto graph_gather = [&](bool apply, int sp) {
         // accumulators per output (unknown image, channel)
         for (int k : unk)
-            for (int c = 0; c < m.images[k].channels; ++c)
+            for (int c = 0; c < m.images[k].channels && in_space(k, sp); ++c)
                 o << "        T acc" << uslot[k] << "_" << c << " = 0, dg" << uslot[k] << "_" << c << " = 0;\n";
         o << "        (void)0;\n";
         for (size_t g = 0; g < m.graphs.size(); ++g) {
@@ -1664,9 +1723,10 @@ GenSource generate(GModel& m, bool dbl, bool off32) {
                     if (r.graph == (int)g)
                         for (int u : r.unknowns) any |= P.at(u).slot == (int)k;
                 if (!any) continue;
+                if (mspace && m.graphs[g].slot_space[k] != sp) continue;
                 const int sbk = gs.slot_base[g] + (int)k;
                 std::ostringstream pre, body;
-                Body b(m, body, nd, uslot);
+                Body b(m, body, nd_of(sp), uslot);   // (slot reads use no coordinates)
                 b.hoist_to(&pre, (int)k, (int)g);
                 int idx = 0;
                 for (auto& r : m.residuals) {
@@ -1736,31 +1796,44 @@ GenSource generate(GModel& m, bool dbl, bool off32) {
         }
     };
     {
+        // the vertex loop of a space and its flags
+        auto open_vtx = [&](int sp) -> std::string {
+            if (!mspace)
+                return "    for (long long vtx = opt_xcd_block() * 256 + threadIdx.x; vtx < a.npix; vtx += (long long)gridDim.x * 256) {\n";
+            const std::string s = std::to_string(sp);
+            return "    {\n    const long long fb = a.fbase[" + s + "];\n"
+                   "    for (long long vtx = opt_xcd_block() * 256 + threadIdx.x; vtx < a.snpix[" + s + "]; vtx += (long long)gridDim.x * 256) {\n";
+        };
+        const std::string flag_vtx = mspace ? "a.flags[fb + vtx]" : "a.flags[vtx]";
         o << "extern \"C\" __global__ __launch_bounds__(256) void gen_jtf_graph(GenArgs a, T* __restrict__ r, T* __restrict__ diag) {\n"
-             "    OPT_COORDS\n"
-             "    for (long long vtx = opt_xcd_block() * 256 + threadIdx.x; vtx < a.npix; vtx += (long long)gridDim.x * 256) {\n";
-        graph_gather(false);
-        o << "        const bool act = (a.flags[vtx] & 1) != 0;\n";
+          << top_coords;
+        for (int sp : uspaces) {
+        o << open_vtx(sp);
+        graph_gather(false, sp);
+        o << "        const bool act = (" << flag_vtx << " & 1) != 0;\n";
         for (int k : unk)
-            for (int c = 0; c < m.images[k].channels; ++c) {
+            for (int c = 0; c < m.images[k].channels && in_space(k, sp); ++c) {
                 const std::string e = "a.uoff[" + std::to_string(uslot[k]) + "] + vtx * " +
                                       std::to_string(m.images[k].channels) + " + " + std::to_string(c);
                 const std::string sfx = std::to_string(uslot[k]) + "_" + std::to_string(c);
                 o << "        { const long long i = " << e << "; r[i] = act ? r[i] - acc" << sfx
                   << " : (T)0; diag[i] += dg" << sfx << "; }\n";
             }
-        o << "    }\n}\n";
+        o << close_space;
+        }
+        o << "}\n";
         o << "extern \"C\" __global__ __launch_bounds__(256) void gen_apply_graph(GenArgs a, const T* __restrict__ p, T* __restrict__ Ap,\n"
              "        const T* __restrict__ dadd, const int* stop, ReduceSlot rs, int has_centred) {\n"
              "    if (stop && *stop) return;\n"
-             "    OPT_COORDS\n"
-             "    T dot = 0;\n"
-             "    for (long long vtx = opt_xcd_block() * 256 + threadIdx.x; vtx < a.npix; vtx += (long long)gridDim.x * 256) {\n";
-        graph_gather(true);
+          << top_coords <<
+             "    T dot = 0;\n";
         // 1-D vertex domains: the centred terms at this vertex too (after the edge loops,
         // whose registers are free by then), instead of a gen_apply pass that stores them
         // for this kernel to read back
-        gs.graph_apply_centred = gs.has_centered && nd == 1;
+        gs.graph_apply_centred = gs.has_centered && nd == 1 && !mspace;
+        for (int sp : uspaces) {
+        o << open_vtx(sp);
+        graph_gather(true, sp);
         if (gs.graph_apply_centred) {
             std::string decl = "        T";
             for (int k : unk)
@@ -1768,12 +1841,12 @@ GenSource generate(GModel& m, bool dbl, bool off32) {
                     decl += std::string(decl.size() > 9 ? "," : "") + " cacc" + std::to_string(uslot[k]) + "_" + std::to_string(c) + " = 0";
             o << decl << ";\n        {\n        const long long lin = vtx;\n" << coords;
             Body b(m, o, nd, uslot);
-            centred_apply(b, true);
+            centred_apply(b, true, 0);
             o << "        }\n";
         }
-        o << "        const bool act = (a.flags[vtx] & 1) != 0;\n";
+        o << "        const bool act = (" << flag_vtx << " & 1) != 0;\n";
         for (int k : unk)
-            for (int c = 0; c < m.images[k].channels; ++c) {
+            for (int c = 0; c < m.images[k].channels && in_space(k, sp); ++c) {
                 const std::string e = "a.uoff[" + std::to_string(uslot[k]) + "] + vtx * " +
                                       std::to_string(m.images[k].channels) + " + " + std::to_string(c);
                 const std::string sfx = std::to_string(uslot[k]) + "_" + std::to_string(c);
@@ -1783,8 +1856,9 @@ GenSource generate(GModel& m, bool dbl, bool off32) {
                   << " + (dadd ? dadd[i] * pe : (T)0) : (T)0;\n"
                   << "          Ap[i] = o; dot += pe * o; }\n";
             }
-        o << "    }\n"
-             "    double v[1] = {(double)dot};\n    block_reduce_publish<1>(v, rs, blockIdx.x);\n}\n";
+        o << close_space;
+        }
+        o << "    double v[1] = {(double)dot};\n    block_reduce_publish<1>(v, rs, blockIdx.x);\n}\n";
     }
     (void)zero3;
     g_cache = nullptr;

@@ -7,9 +7,10 @@
 #include "model.h"
 
 // Kernel argument block shared by the host (generic.hip) and the generated source: the
-// macro body is compiled on the host and pasted, stringised, into the generated code.
-#define OPTAMD_GENARGS_BODY                                                                 \
-    struct GenArgs {                                                                        \
+// macro bodies are compiled on the host and pasted, stringised, into the generated code.
+// The per-space tail is pasted only for energies over several index spaces (GModel::multi):
+// a single-space energy's kernels declare, and the runtime copies, the head alone.
+#define OPTAMD_GENARGS_FIELDS                                                               \
         int dims[3];                /* unknowns' index space, unused dims = 1 */            \
         long long npix;             /* elements of that space */                            \
         const void* img[16];        /* by image id: unknowns (T) and known arrays */        \
@@ -22,11 +23,17 @@
         unsigned char* flags;       /* bit0: active (not excluded) */                       \
         long long uoff[4];          /* offset of each unknown image in the vector */        \
         int ymem0;                  /* 2-D row slabs: global row of memory row 0 */          \
-        long long own_lo, own_hi;   /* owned pixels (memory indices) */                      \
-    };
+        long long own_lo, own_hi;   /* owned pixels (memory indices) */
+#define OPTAMD_GENARGS_SPACES                                                               \
+        int sdims[8][3];            /* per space: its dims, unused dims = 1 */               \
+        long long snpix[8];         /* per space: its elements */                            \
+        long long fbase[8];         /* per unknown-carrying space: first flag byte */
 
 namespace optamd {
-OPTAMD_GENARGS_BODY
+struct GenArgs {
+    OPTAMD_GENARGS_FIELDS
+    OPTAMD_GENARGS_SPACES
+};
 namespace gen {
 
 struct GenSource {

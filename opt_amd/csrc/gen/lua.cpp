@@ -583,6 +583,7 @@ private:
     GModel* m_;
     std::shared_ptr<Scope> globals_;
     std::vector<int> energy_terms_;   // scalar residual expressions, in Energy order
+    std::vector<int> exclude_terms_;  // Exclude expressions, in call order
     std::vector<std::pair<int, int>> sample_cache_;   // cached Sample node (offset 0) -> its image
     int cache_samples(int e);
     int line_ = 0;
@@ -998,6 +999,7 @@ private:
         im.index = (int)a[3].n;
         im.unknown = unknown;
         im.tvalued = unknown;
+        im.space = m_->space_of(im.dims);
         note_index(im.index);
         m_->images.push_back(im);
         Value v;
@@ -1015,14 +1017,24 @@ private:
         const std::vector<int> ex = as_expr(a[2]);
         im.channels = (int)ex.size();
         im.internal = im.tvalued = true;
+        im.space = m_->space_of(im.dims);
         m_->images.push_back(im);
         const int id = (int)m_->images.size() - 1;
         GComputed c;
         c.image = id;
+        c.space = im.space;
         c.expr = ex;
         bool bounds = false;
         for (int e : ex)
             P().visit(e, [&](int, const Node& n) {
+                // evaluated per element of its own space: every array it reads at an offset
+                // or samples must lie over that space
+                if ((n.op == Op::Read && n.slot < 0) || n.op == Op::Sample)
+                    for (int ri : {n.i, n.op == Op::Sample ? n.off2[0] : -1, n.op == Op::Sample ? n.off2[1] : -1})
+                        if (ri >= 0 && m_->images[ri].space != im.space)
+                            err("ComputedArray '" + im.name + "' over " + space_name(im.space) + " reads '" +
+                                m_->images[ri].name + "' over a different index space " +
+                                space_name(m_->images[ri].space));
                 if (n.op == Op::Read && n.slot < 0) {
                     const GComputed* inner = computed_of(n.i);
                     for (int k = 0; k < 3; ++k) {
@@ -1053,6 +1065,7 @@ private:
                     GImage gi;
                     gi.name = im.name + "_d_" + std::to_string(u);
                     gi.dims = m_->images[id].dims;
+                    gi.space = m_->images[id].space;
                     gi.internal = gi.tvalued = true;
                     m_->images.push_back(gi);
                     g.gimg = (int)m_->images.size() - 1;
@@ -1078,6 +1091,11 @@ private:
         const GImage& im = m_->images[id];
         const int nd = (int)im.dims.size();
         if (!a.empty() && a[0].k == V::Slot) {   // X(G.v)
+            // the slot's vertices index its own space: the image must lie over it (o.t:1760)
+            const GGraph& gr = m_->graphs[a[0].id];
+            if (gr.slot_dims[a[0].slot] != im.dims)
+                err("graph element is in a different index space from image: " + im.name + "(" + gr.name + "." +
+                    gr.slot_names[a[0].slot] + ")");
             int ch = -1;
             if (a.size() == 2) ch = (int)a[1].n;
             else if (a.size() != 1) err("graph access X(G.v[, channel])");
@@ -1116,6 +1134,11 @@ private:
 
     void install();
     void def(const std::string& n, Builtin f) { globals_->vars[n] = std::make_shared<Value>(builtin(std::move(f))); }
+    std::string space_name(int s) const {
+        std::string o = "{";
+        for (size_t k = 0; k < m_->spaces[s].size(); ++k) o += (k ? "," : "") + m_->dims[m_->spaces[s][k]].name;
+        return o + "}";
+    }
     void unsupported(const std::string& what) {
         if (m_->unsupported.empty()) m_->unsupported = what;
     }
@@ -1222,6 +1245,10 @@ void Interp::install() {
         for (size_t i = 2; i + 2 < a.size(); i += 3) {
             g.slot_names.push_back(a[i].s);
             g.slot_index.push_back((int)a[i + 2].n);
+            std::vector<int> sd;
+            if (a[i + 1].k == V::Table) for (auto& d : a[i + 1].t->a) sd.push_back(dim_of(d));
+            g.slot_dims.push_back(sd);
+            g.slot_space.push_back(m_->space_of(sd));
             note_index((int)a[i + 2].n);
         }
         m_->graphs.push_back(g);
@@ -1236,7 +1263,7 @@ void Interp::install() {
     });
     def("Exclude", [this](VList& a) {
         if (a.empty()) err("Exclude(expr)");
-        m_->exclude = comp(a[0], 0);
+        exclude_terms_.push_back(comp(a[0], 0));
         return VList{};
     });
     def("Energy", [this](VList& a) {
@@ -1446,6 +1473,7 @@ int Interp::cache_samples(int e) {
         if (n.op != Op::Sample || n.off2[0] < 0 || n.off2[1] < 0 || repl.count(id)) return;
         int off[3] = {0, 0, 0};
         bool set[3] = {false, false, false}, ok = true, reads = false;
+        int rimg = -1;
         auto want = [&](int d, int v) {
             if (set[d] && off[d] != v) ok = false;
             set[d] = true;
@@ -1456,6 +1484,8 @@ int Interp::cache_samples(int e) {
                 if (q.op == Op::Read) {
                     if (q.slot >= 0 || computed_of(q.i)) { ok = false; return; }
                     reads = true;
+                    if (rimg < 0) rimg = q.i;
+                    if (m_->images[q.i].space != m_->images[rimg].space) { ok = false; return; }
                     for (int d = 0; d < 3; ++d) want(d, q.off[d]);
                 } else if (q.op == Op::Coord) {
                     want(q.i, q.off[q.i]);
@@ -1464,6 +1494,8 @@ int Interp::cache_samples(int e) {
                 }
             });
         if (!ok || !reads) return;
+        for (int si : {n.i, n.off2[0], n.off2[1]})   // (finish() names a mix of spaces)
+            if (m_->images[si].space != m_->images[rimg].space) return;
         const int neg[3] = {-off[0], -off[1], -off[2]};
         const int s0 = P().shift(id, neg);
         int img = -1;
@@ -1492,7 +1524,8 @@ int Interp::cache_samples(int e) {
             if (m_->images.size() + need > 16) return;
             GImage im;
             im.name = "sample_cache_" + std::to_string(sample_cache_.size());
-            im.dims = m_->images[unk[0]].dims;
+            im.dims = m_->images[rimg].dims;   // the space the sample's coordinates are centred on
+            im.space = m_->images[rimg].space;
             im.channels = 1;
             im.internal = im.tvalued = true;
             m_->images.push_back(im);
@@ -1501,12 +1534,14 @@ int Interp::cache_samples(int e) {
             c.image = img;
             c.expr = {s0};
             c.per_step = true;
+            c.space = im.space;
             for (GGrad& g : grads) {
                 int gnode = g.expr;
                 if (!P().is_const(g.expr)) {
                     GImage gi;
                     gi.name = im.name + "_d_" + std::to_string(g.u);
                     gi.dims = im.dims;
+                    gi.space = im.space;
                     gi.internal = gi.tvalued = true;
                     m_->images.push_back(gi);
                     g.gimg = (int)m_->images.size() - 1;
@@ -1533,6 +1568,27 @@ void Interp::finish() {
             for (auto& u : m_->images)
                 if (u.unknown && u.index == im.index) im.tvalued = true;
     for (int& e : energy_terms_) e = cache_samples(e);
+    // Exclude(e) applies to the space its reads are centred on (o.t:3213-3216)
+    for (int e : exclude_terms_) {
+        std::vector<int> sp;
+        P().visit(e, [&](int, const Node& n) {
+            if ((n.op == Op::Read && n.slot < 0) || n.op == Op::Sample) {
+                const int s = m_->images[n.i].space;
+                if (std::find(sp.begin(), sp.end(), s) == sp.end()) sp.push_back(s);
+            }
+        });
+        if (sp.size() > 1)
+            throw LuaError("Exclude reads arrays over different index spaces: " + space_name(sp[0]) + ", " +
+                           space_name(sp[1]));
+        const std::vector<int> unk = m_->unknown_images();
+        const int s = !sp.empty() ? sp[0] : unk.empty() ? 0 : m_->images[unk[0]].space;
+        bool holds = false;
+        for (int k : unk) holds |= m_->images[k].space == s;
+        if (!holds) throw LuaError("Exclude over index space " + space_name(s) + ", which holds no unknown");
+        if (m_->exclude_of(s) >= 0) throw LuaError("more than one Exclude over index space " + space_name(s));
+        m_->excludes.push_back({s, e});
+        if (m_->exclude < 0) m_->exclude = e;
+    }
     for (int e : energy_terms_) {
         GResidual r;
         bool any = false;
@@ -1540,9 +1596,19 @@ void Interp::finish() {
         bool bounds = false;
         int lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
         std::set<int> unk;
+        std::vector<int> centred_imgs;   // one image per index space the offset reads lie over
+        auto note_space = [&](int image) {
+            for (int i : centred_imgs)
+                if (m_->images[i].space == m_->images[image].space) return;
+            centred_imgs.push_back(image);
+        };
         P().visit(e, [&](int id, const Node& n) {
+            if (n.op == Op::Sample)
+                for (int si : {n.i, n.off2[0], n.off2[1]})
+                    if (si >= 0) note_space(si);
             if (n.op == Op::Read) {
                 any = true;
+                if (n.slot < 0) note_space(n.i);
                 if (n.slot >= 0) {
                     if (graph >= 0 && graph != n.g) throw LuaError("residual reads from two graphs");
                     graph = n.g;
@@ -1554,7 +1620,12 @@ void Interp::finish() {
                         hi[k] = std::max(hi[k], n.off[k] + c->hi[k]);
                     }
                     for (const GGrad& g : c->grads)
-                        if (g.ch == n.ch) unk.insert(P().shift(g.u, n.off));
+                        if (g.ch == n.ch) {
+                            if (m_->images[P().at(g.u).i].space != m_->images[n.i].space)
+                                throw LuaError("ComputedArray '" + m_->images[n.i].name +
+                                               "' depends on an unknown over a different index space");
+                            unk.insert(P().shift(g.u, n.off));
+                        }
                 } else {
                     for (int k = 0; k < 3; ++k) { lo[k] = std::min(lo[k], n.off[k]); hi[k] = std::max(hi[k], n.off[k]); }
                 }
@@ -1571,6 +1642,18 @@ void Interp::finish() {
         if (!any) throw LuaError("residual must actually use some image");
         r.graph = graph;
         if (graph < 0) {
+            // a centred residual is instantiated over the one space its reads lie over
+            // (the reference's classifyexpression asserts a single IndexSpace per term)
+            if (centred_imgs.size() > 1)
+                throw LuaError("centred residual reads arrays over different index spaces: " +
+                               m_->images[centred_imgs[0]].name + " over " + space_name(m_->images[centred_imgs[0]].space) +
+                               ", " + m_->images[centred_imgs[1]].name + " over " +
+                               space_name(m_->images[centred_imgs[1]].space));
+            r.space = centred_imgs.empty() ? m_->images[m_->unknown_images().at(0)].space
+                                           : m_->images[centred_imgs[0]].space;
+            if (m_->multi() && unk.empty())
+                throw LuaError("centred residual over index space " + space_name(r.space) +
+                               " reads no unknown of that space");
             // by default zero any residual that reads out of bounds (usesbounds: only the centre)
             if (bounds) for (int k = 0; k < 3; ++k) lo[k] = hi[k] = 0;
             r.expr = P().select(P().inbox(lo, hi), e, P().cnst(0.0));
@@ -1588,6 +1671,23 @@ int GModel::unknown_dims() const {
     for (auto& im : images)
         if (im.unknown) return (int)im.dims.size();
     return 0;
+}
+int GModel::space_of(const std::vector<int>& d) {
+    for (size_t s = 0; s < spaces.size(); ++s)
+        if (spaces[s] == d) return (int)s;
+    spaces.push_back(d);
+    return (int)spaces.size() - 1;
+}
+int GModel::exclude_of(int space) const {
+    for (auto& x : excludes)
+        if (x.first == space) return x.second;
+    return -1;
+}
+std::vector<int> GModel::unknown_spaces() const {
+    std::vector<int> out;
+    for (int k : unknown_images())
+        if (std::find(out.begin(), out.end(), images[k].space) == out.end()) out.push_back(images[k].space);
+    return out;
 }
 std::vector<int> GModel::unknown_images() const {
     std::vector<int> u;

@@ -22,6 +22,7 @@ struct GImage {
     bool unknown = false;
     std::vector<int> dims;       // GDim ids
     std::string elem = "float";  // element type of a known array ("float", "uint8", ...)
+    int space = -1;              // GModel::spaces id of dims (build_model fills it)
     bool internal = false;       // ComputedArray value / gradient image: allocated by the plan
     bool tvalued = false;        // stored in the solver precision T (unknowns, internal
                                  // images, arrays aliasing an unknown's parameter slot)
@@ -37,6 +38,7 @@ struct GComputed {
     int lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};   // bbox of the expression (bboxforexpression)
     bool per_step = false;         // a private cache of bound arrays (lua.cpp cache_samples),
                                    // not a ComputedArray of the energy: also rebuilt at Step start
+    int space = -1;                // index space of its image
 };
 struct GParam { std::string name; std::string type; int index = -1; };
 struct GGraph {
@@ -44,11 +46,14 @@ struct GGraph {
     std::vector<int> dims;                // edge-count GDim ids
     std::vector<std::string> slot_names;
     std::vector<int> slot_index;          // problemparams index of each vertex array
+    std::vector<std::vector<int>> slot_dims;   // the index space each slot's vertices lie in (GDim ids)
+    std::vector<int> slot_space;          // its GModel::spaces id
 };
 struct GResidual {
     int expr = -1;                 // scalar expression (centred: wrapped in its bbox select)
     int graph = -1;                // -1: centred over the unknowns' index space
     std::vector<int> unknowns;     // distinct unknown Read nodes (the support)
+    int space = -1;                // centred: the index space it is instantiated over
 };
 
 struct GModel {
@@ -59,12 +64,23 @@ struct GModel {
     std::vector<GGraph> graphs;
     std::vector<GResidual> residuals;
     std::vector<GComputed> computed;   // declaration order (= precompute order)
-    int exclude = -1;              // Exclude(expr): centred scalar, -1 = none
+    int exclude = -1;              // Exclude(expr): centred scalar, -1 = none (the first one declared)
+    // Index spaces (the reference's IndexSpace, o.t:548-600): every distinct ordered Dim list
+    // an Unknown, Array, ComputedArray or graph slot is declared over, in declaration order.
+    // One space: the single-domain energies every kernel form serves. Several: unknowns and
+    // arrays of different sizes (cameras / points / observations); centred residuals are
+    // instantiated over their own space, graph slots index theirs.
+    std::vector<std::vector<int>> spaces;
+    std::vector<std::pair<int, int>> excludes;   // (space, expr): at most one Exclude per space
     bool use_preconditioner = false;
     std::string unsupported;       // first construct the generic path cannot lower
     int n_params_total = 0;
 
-    int unknown_dims() const;      // dimensionality of the unknowns' index space
+    int unknown_dims() const;      // dimensionality of the (first) unknowns' index space
+    bool multi() const { return spaces.size() > 1; }
+    int space_of(const std::vector<int>& dims);          // id of dims, registered on first use
+    int exclude_of(int space) const;                     // Exclude expression of a space, -1 = none
+    std::vector<int> unknown_spaces() const;             // spaces holding unknowns, in unknown_images() order
     std::vector<int> unknown_images() const;   // image ids of the unknowns, declaration order
 };
 

@@ -7,7 +7,8 @@
 // 1295-1348, 2669-3235). The hand-written families (image_warping.hip, ...) remain the
 // fast paths for the energies they recognise; this path covers every other energy in
 // the DSL subset gen/lua.cpp accepts (centred stencils over 1-3-D index spaces, graph
-// residuals, Exclude, Select / InBounds, scalar parameters, up to 4 unknown images).
+// residuals, Exclude, Select / InBounds, scalar parameters, up to 4 unknown images, which
+// may lie over several index spaces: cameras / points / observations).
 // OPT_AMD_GENERIC=1 routes recognised families here too (to validate it against the
 // hand-written kernels and the reference's known answers).
 #include <hip/hiprtc.h>
@@ -89,11 +90,18 @@ size_t elem_size(const gen::GImage& im, bool dbl) {
 bool gather_offsets_fit_32(const gen::GModel& m, const ProblemSpec& s, bool dbl) {
     if (env_int("OPT_AMD_GEN_OFF32", 1) == 0) return false;   // tests: force the 64-bit form
     const long long lim = 1LL << 31, t = dbl ? 8 : 4;
-    long long npix = 1, chans = 0;
-    for (int d : m.images[m.unknown_images()[0]].dims) npix *= (long long)s.dim_values.at(m.dims[d].index);
-    for (int k : m.unknown_images()) chans += m.images[k].channels;
-    bool ok = npix * chans * t < lim && npix * 16 * t < lim;
-    for (auto& im : m.images) ok &= npix * im.channels * (long long)elem_size(im, dbl) < lim;
+    auto pixels = [&](const std::vector<int>& dims) {
+        long long n = 1;
+        for (int d : dims) n *= (long long)s.dim_values.at(m.dims[d].index);
+        return n;
+    };
+    long long npix = 0, total = 0;   // the largest unknown-carrying space, the whole unknown vector
+    for (int k : m.unknown_images()) {
+        npix = std::max(npix, pixels(m.images[k].dims));
+        total += pixels(m.images[k].dims) * m.images[k].channels;
+    }
+    bool ok = total * t < lim && npix * 16 * t < lim;
+    for (auto& im : m.images) ok &= pixels(im.dims) * im.channels * (long long)elem_size(im, dbl) < lim;
     for (auto& g : m.graphs) {
         long long e = 1;
         for (int d : g.dims) e *= (long long)s.dim_values.at(m.dims[d].index);
@@ -115,6 +123,8 @@ bool generic_accepts(const std::string& text, ProblemSpec* spec, std::string* er
     }
     const std::vector<int> unk = m.unknown_images();
     if (unk.empty()) { *err = "no Unknown declared"; return false; }
+    if (m.unknown_spaces().size() > 4) { *err = "more than 4 index spaces hold unknowns"; return false; }
+    if (m.spaces.size() > 8) { *err = "more than 8 index spaces"; return false; }
     if (unk.size() > 4) { *err = "more than 4 unknown images"; return false; }
     if (m.images.size() > 16) { *err = "more than 16 images"; return false; }
     if (m.params.size() > 32) { *err = "more than 32 parameters"; return false; }
@@ -122,16 +132,8 @@ bool generic_accepts(const std::string& text, ProblemSpec* spec, std::string* er
     size_t slots = 0;
     for (auto& g : m.graphs) slots += g.slot_names.size();
     if (slots > 16) { *err = "more than 16 graph vertex arrays"; return false; }
-    const int nd = m.unknown_dims();
-    if (nd < 1 || nd > 3) { *err = "unknowns must be 1-, 2- or 3-dimensional"; return false; }
-    for (int k : unk)
-        if (m.images[k].dims != m.images[unk[0]].dims) { *err = "unknowns over different index spaces"; return false; }
-    for (auto& im : m.images)
-        if (!im.unknown && im.dims != m.images[unk[0]].dims) {
-            *err = std::string(im.internal ? "computed array '" : "array '") + im.name +
-                   "' is not over the unknowns' index space";
-            return false;
-        }
+    for (auto& sp : m.spaces)
+        if (sp.size() < 1 || sp.size() > 3) { *err = "index spaces must be 1-, 2- or 3-dimensional"; return false; }
     if (m.residuals.empty()) { *err = "no Energy terms"; return false; }
     spec->text = text;
     spec->use_preconditioner = m.use_preconditioner;
@@ -159,7 +161,10 @@ bool generic_signature(const std::string& text, std::string* sig, bool* use_pre,
         s += "I" + std::to_string(im.index) + ":" + std::to_string(im.channels) + (im.unknown ? "u" : "a") +
              (im.internal ? "i" : "") + (im.tvalued ? "t" : "") + im.elem + "{" + ids(im.dims) + "};";
     for (auto& p : m.params) s += "P" + std::to_string(p.index) + ":" + p.type + ";";
-    for (auto& g : m.graphs) s += "G{" + ids(g.dims) + "}{" + ids(g.slot_index) + "};";
+    // (slot spaces, residual and Exclude spaces: only for energies over several index spaces,
+    // so that a single-space energy's signature is what it always was)
+    for (auto& g : m.graphs)
+        s += "G{" + ids(g.dims) + "}{" + ids(g.slot_index) + "}" + (m.multi() ? "{" + ids(g.slot_space) + "}" : "") + ";";
     for (auto& c : m.computed) {
         s += "C" + std::to_string(c.image) + ":";
         for (int e : c.expr) s += m.pool.str(e) + "|";
@@ -172,9 +177,12 @@ bool generic_signature(const std::string& text, std::string* sig, bool* use_pre,
         for (int k = 0; k < 3; ++k) s += std::to_string(c.lo[k]) + ":" + std::to_string(c.hi[k]) + ",";
         s += ";";
     }
-    s += "X" + (m.exclude >= 0 ? m.pool.str(m.exclude) : std::string("-")) + ";";
+    if (!m.multi()) s += "X" + (m.exclude >= 0 ? m.pool.str(m.exclude) : std::string("-")) + ";";
+    for (auto& x : m.excludes)
+        if (m.multi()) s += "X" + std::to_string(x.first) + ":" + m.pool.str(x.second) + ";";
     for (auto& r : m.residuals)
-        s += "R" + std::to_string(r.graph) + ":" + std::to_string(r.unknowns.size()) + ":" + m.pool.str(r.expr) + ";";
+        s += "R" + std::to_string(r.graph) + (m.multi() && r.graph < 0 ? "s" + std::to_string(r.space) : "") + ":" +
+             std::to_string(r.unknowns.size()) + ":" + m.pool.str(r.expr) + ";";
     *sig = s;
     if (use_pre) *use_pre = m.use_preconditioner;
     return true;
@@ -246,6 +254,29 @@ public:
             own_lo_ = dom.off(0, dom.y_lo);
             own_hi_ = dom.off(0, dom.y_hi);
         }
+        multi_ = m_.multi();
+        if (multi_) {
+            // several index spaces: per-space sizes; the flag bytes of the unknown-carrying
+            // spaces concatenated in unknown order. No slabs (slab_refusal), so the Domain is
+            // only the flat extent of the flags.
+            for (size_t sp = 0; sp < m_.spaces.size() && sp < 8; ++sp) {
+                sdims_[sp][0] = sdims_[sp][1] = sdims_[sp][2] = 1;
+                snpix_[sp] = 1;
+                for (size_t k = 0; k < m_.spaces[sp].size(); ++k) {
+                    sdims_[sp][k] = (int)spec.dim_values.at(m_.dims[m_.spaces[sp][k]].index);
+                    snpix_[sp] *= sdims_[sp][k];
+                }
+            }
+            nflags_ = 0;
+            npix_ = 0;
+            for (int sp : m_.unknown_spaces()) {
+                fbase_[sp] = nflags_;
+                nflags_ += snpix_[sp];
+                npix_ = std::max(npix_, snpix_[sp]);   // (the launch grid's extent)
+            }
+            ymem0_ = 0;
+            own_lo_ = own_hi_ = 0;
+        }
         halo_ = row_halo();
         for (size_t g = 0; g < m_.graphs.size(); ++g) {
             long long e = 1;
@@ -255,7 +286,7 @@ public:
         long long off = 0;
         for (size_t k = 0; k < unk_.size(); ++k) {
             uoff_[k] = off;
-            off += npix_ * m_.images[unk_[k]].channels;
+            off += pixels_of(unk_[k]) * m_.images[unk_[k]].channels;
         }
         n_ = off;
         src_ = gen::generate(m_, sizeof(T) == 8, gather_offsets_fit_32(m_, spec, sizeof(T) == 8));
@@ -292,13 +323,15 @@ public:
             L.off[k] = uoff_[k];
         }
         L.off[L.nimg] = n_;
-        L.N = npix_;
+        L.N = multi_ ? nflags_ : npix_;
+        for (size_t k = 0; k < unk_.size() && multi_; ++k) L.fbase[k] = fbase_[m_.images[unk_[k]].space];
         return L;
     }
     int halo() const { return halo_; }
     // Why this energy cannot run on row slabs ("" = it can). Graph and sampled reads are
     // data-dependent (as the optical_flow / ARAP families), slabs split the 2nd dimension.
     std::string slab_refusal() const {
+        if (multi_) return "generic: no row-slab decomposition for an energy over several index spaces";
         if (m_.unknown_dims() != 2) return "generic: row-slab decomposition needs a 2-D energy";
         if (!m_.graphs.empty()) return "generic: no row-slab decomposition for graph energies";
         // (sampled reads may sit in a residual or, cached per Step, in a ComputedArray)
@@ -317,6 +350,7 @@ public:
     }
     int stencil_blocks() const {
         long long w = std::max(npix_, n_);
+        if (multi_) w = npix_;   // every loop walks one space's elements (or a graph's edges)
         for (int e : nedge_) w = std::max<long long>(w, e);
         return (int)std::max<long long>(1, std::min<long long>((w + kBlock - 1) / kBlock, max_blocks_));
     }
@@ -364,6 +398,11 @@ public:
         a_.own_lo = own_lo_;
         a_.own_hi = own_hi_;
         for (size_t k = 0; k < unk_.size(); ++k) a_.uoff[k] = uoff_[k];
+        for (size_t sp = 0; sp < m_.spaces.size() && sp < 8 && multi_; ++sp) {
+            for (int k = 0; k < 3; ++k) a_.sdims[sp][k] = sdims_[sp][k];
+            a_.snpix[sp] = snpix_[sp];
+            a_.fbase[sp] = fbase_[sp];
+        }
     }
     // hipGraph replay gate + key (StencilPlan::pcg_graph_begin), from the lowered model:
     // no capture for graph energies (adjacency rebuilt on bind); the key is the argument
@@ -430,17 +469,21 @@ public:
     void model_cost(const T* delta, ReduceSlot rs, hipStream_t s) { launch(k_cost_, s, {&a_, &delta, &rs}); }
 
     // materialized Jacobian (useMaterializedJTJ, csr.h): the generated saveJToCRS kernels
+    // (none over several index spaces: -1, and dump_j refuses)
     long long jacobian_rows() const {
+        if (multi_) return -1;
         long long r = 0;
         for (auto& d : src_.dump) r += elements(d.graph) * d.rows;
         return r;
     }
     long long jacobian_nnz() const {
+        if (multi_) return -1;
         long long z = 0;
         for (auto& d : src_.dump) z += elements(d.graph) * d.nnz;
         return z;
     }
     void dump_j(int* rowPtr, int* colInd, T* val, hipStream_t s) {
+        if (multi_) throw PlanError("generic: no Jacobian assembly (OptAMD_EvalJacobian) for an energy over several index spaces");
         long long rb = 0, zb = 0;
         for (size_t i = 0; i < src_.dump.size(); ++i) {
             launch(k_dump_[i], s, {&a_, &rowPtr, &colInd, &val, &rb, &zb, &n_});
@@ -485,8 +528,12 @@ private:
         return std::max(h, 1);
     }
     size_t image_bytes(size_t i) const {
-        return (size_t)npix_ * m_.images[i].channels * elem_size(m_.images[i], sizeof(T) == 8);
+        return (size_t)pixels_of(i) * m_.images[i].channels * elem_size(m_.images[i], sizeof(T) == 8);
     }
+    // elements of image i: its own index space's
+    long long pixels_of(size_t i) const { return multi_ ? snpix_[m_.images[i].space] : npix_; }
+    // elements of the space graph g's slot k indexes
+    long long slot_pixels(size_t g, size_t k) const { return multi_ ? snpix_[m_.graphs[g].slot_space[k]] : npix_; }
     void load_module() {
         std::string obj;
         {
@@ -576,22 +623,26 @@ private:
             const int ns = (int)m_.graphs[g].slot_names.size();
             const unsigned long long h = graph_fingerprint(a_.slot + sb, ns, nedge_[g], s, fp_scratch_);
             if (!(goff_[sb] && h == fingerprint_[g])) {
-                fingerprint_[g] = h;
-                for (int k = 0; k < ns; ++k) {
-                    if (nedge_[g] > 0) {
-                        std::vector<int> hv(nedge_[g]);
-                        OPT_HIP_CHECK(hipMemcpyAsync(hv.data(), a_.slot[sb + k], sizeof(int) * nedge_[g],
-                                                     hipMemcpyDeviceToHost, s));
-                        OPT_HIP_CHECK(hipStreamSynchronize(s));
-                        for (int v : hv)
-                            if (v < 0 || v >= npix_) {
-                                fprintf(stderr, "[opt_amd] generic: graph '%s' vertex index %d outside [0, %lld)\n",
-                                        m_.graphs[g].name.c_str(), v, npix_);
-                                exit(1);
-                            }
-                    }
-                    build_incidence(sb + k, nedge_[g], s);
+                // every slot against its own space, before any list is built or the
+                // fingerprint kept: a bad index stops the solve (PlanError), no kernel reads it
+                for (int k = 0; k < ns && nedge_[g] > 0; ++k) {
+                    std::vector<int> hv(nedge_[g]);
+                    OPT_HIP_CHECK(hipMemcpyAsync(hv.data(), a_.slot[sb + k], sizeof(int) * nedge_[g],
+                                                 hipMemcpyDeviceToHost, s));
+                    OPT_HIP_CHECK(hipStreamSynchronize(s));
+                    const long long nv = slot_pixels(g, k);
+                    for (int v : hv)
+                        if (v < 0 || v >= nv) {
+                            fingerprint_[g] = 0;
+                            dfree(goff_[sb]);
+                            goff_[sb] = nullptr;
+                            throw PlanError("generic: graph '" + m_.graphs[g].name + "' slot '" +
+                                            m_.graphs[g].slot_names[k] + "': vertex index " + std::to_string(v) +
+                                            " outside [0, " + std::to_string(nv) + ")");
+                        }
                 }
+                fingerprint_[g] = h;
+                for (int k = 0; k < ns; ++k) build_incidence(sb + k, nedge_[g], slot_pixels(g, k), s);
                 for (int k = 0; k < ns; ++k) build_neighbours(sb + k, nedge_[g], s);
             }
             sb += ns;
@@ -618,28 +669,28 @@ private:
     }
     // Edges by vertex for slot array sb: a stable radix sort of (vertex, edge id) pairs and
     // a histogram + exclusive scan of the vertex counts.
-    void build_incidence(int sb, int E, hipStream_t s) {
+    void build_incidence(int sb, int E, long long nv, hipStream_t s) {
         dfree(goff_[sb]);
         dfree(geid_[sb]);
-        goff_[sb] = (int*)dmalloc(sizeof(int) * (npix_ + 1));
+        goff_[sb] = (int*)dmalloc(sizeof(int) * (nv + 1));
         geid_[sb] = (int*)dmalloc(sizeof(int) * std::max(E, 1));
-        OPT_HIP_CHECK(hipMemsetAsync(goff_[sb], 0, sizeof(int) * (npix_ + 1), s));
+        OPT_HIP_CHECK(hipMemsetAsync(goff_[sb], 0, sizeof(int) * (nv + 1), s));
         if (E == 0) return;
         int* keys = (int*)dmalloc(sizeof(int) * E);
         int* ids = (int*)dmalloc(sizeof(int) * E);
         const int grid = std::min((E + 255) / 256, 4096);
         hipLaunchKernelGGL(iota_kernel, dim3(grid), dim3(256), 0, s, ids, E);
         int bits = 1;
-        while ((1LL << bits) < npix_) ++bits;
+        while ((1LL << bits) < nv) ++bits;
         size_t need = 0, need2 = 0;
         OPT_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, need, a_.slot[sb], keys, ids, geid_[sb], E, 0, bits, s));
-        OPT_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, need2, goff_[sb], goff_[sb], (int)npix_ + 1, s));
+        OPT_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, need2, goff_[sb], goff_[sb], (int)nv + 1, s));
         need = std::max(need, need2);
         void* tmp = dmalloc(std::max<size_t>(need, 1));
         OPT_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(tmp, need, a_.slot[sb], keys, ids, geid_[sb], E, 0, bits, s));
         hipLaunchKernelGGL(incidence_count, dim3(grid), dim3(256), 0, s, a_.slot[sb], E, goff_[sb]);
         size_t n2 = need;
-        OPT_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp, n2, goff_[sb], goff_[sb], (int)npix_ + 1, s));
+        OPT_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp, n2, goff_[sb], goff_[sb], (int)nv + 1, s));
         OPT_HIP_CHECK(hipStreamSynchronize(s));
         dfree(tmp);
         dfree(keys);
@@ -655,6 +706,10 @@ private:
     std::vector<int> unk_;
     int dims_[3];
     long long npix_ = 0, n_ = 0;
+    // several index spaces (GModel::spaces): sizes, flag bases, flag bytes in all
+    bool multi_ = false;
+    int sdims_[8][3] = {};
+    long long snpix_[8] = {}, fbase_[8] = {}, nflags_ = 0;
     long long uoff_[4] = {0, 0, 0, 0};
     std::vector<int> nedge_ = std::vector<int>(4, 0);
     GenArgs a_{};
@@ -683,10 +738,28 @@ std::unique_ptr<Plan> make_generic_plan(const ProblemSpec& spec, const StateOpti
     int maxidx = -1;
     for (auto& d : m.dims) maxidx = std::max(maxidx, d.index);
     s.dim_values.assign(dims, dims + maxidx + 1);
-    long long npix = 1;
     const std::vector<int>& ud = m.images[m.unknown_images()[0]].dims;
-    for (int d : ud) npix *= s.dim_values[m.dims[d].index];
-    if (npix <= 0 || npix > (1LL << 31) / 16) { *err = "generic: unknown index space empty or too large"; return nullptr; }
+    auto pixels = [&](const std::vector<int>& dims) {
+        long long n = 1;
+        for (int d : dims) n *= s.dim_values[m.dims[d].index];
+        return n;
+    };
+    // every declared space (one: the unknowns'), then the flag bytes of the unknown-carrying ones
+    const long long npix = pixels(ud);
+    for (auto& sp : m.spaces)
+        if (pixels(sp) <= 0 || pixels(sp) > (1LL << 31) / 16) {
+            *err = m.multi() ? "generic: index space empty or too large" : "generic: unknown index space empty or too large";
+            return nullptr;
+        }
+    long long nflags = 0;
+    if (m.multi()) {
+        if (opts.materialized || opts.fused_jtj) {
+            *err = "generic: no materialized Jacobian (useMaterializedJTJ / useFusedJTJ) for an energy over several index spaces";
+            return nullptr;
+        }
+        for (int sp : m.unknown_spaces()) nflags += pixels(m.spaces[sp]);
+        if (nflags > (1LL << 31) / 16) { *err = "generic: index spaces too large"; return nullptr; }
+    }
     // compile (and cache) the kernels here so that a compile error is a NULL plan, as the
     // reference returns nil on errors in the energy (o.t:1526), not a fail-stop
     {
@@ -705,7 +778,8 @@ std::unique_ptr<Plan> make_generic_plan(const ProblemSpec& spec, const StateOpti
         }
     }
     Domain dom{(int)npix, 1, 0, 1, 0, 1};
-    if (ud.size() == 2) {   // image rows: StencilPlan may split them into slabs
+    if (m.multi()) dom = Domain{(int)nflags, 1, 0, 1, 0, 1};
+    else if (ud.size() == 2) {   // image rows: StencilPlan may split them into slabs
         const int W = (int)s.dim_values[m.dims[ud[0]].index], H = (int)s.dim_values[m.dims[ud[1]].index];
         dom = Domain{W, H, 0, H, 0, H};
     }
@@ -729,9 +803,22 @@ int generic_describe(const std::string& text, std::string* out) {
     std::string err;
     if (!gen::build_model(text, &m, &err)) { *out = err; return -1; }
     std::string s;
+    auto space = [&](int sp) {   // "{W,H}"
+        std::string o = "{";
+        for (size_t k = 0; k < m.spaces[sp].size(); ++k) o += (k ? "," : "") + m.dims[m.spaces[sp][k]].name;
+        return o + "}";
+    };
     for (auto& r : m.residuals) {
-        s += (r.graph < 0 ? std::string("centred") : "graph" + std::to_string(r.graph)) + " " +
-             std::to_string(r.unknowns.size()) + " " + m.pool.str(r.expr) + "\n";
+        // several index spaces: a centred template names its space, a graph template its slots'
+        std::string dom = r.graph < 0 ? std::string("centred") : "graph" + std::to_string(r.graph);
+        if (m.multi() && r.graph < 0) dom += space(r.space);
+        if (m.multi() && r.graph >= 0) {
+            const gen::GGraph& g = m.graphs[r.graph];
+            dom += "{";
+            for (size_t k = 0; k < g.slot_names.size(); ++k) dom += (k ? "," : "") + g.slot_names[k] + ":" + space(g.slot_space[k]);
+            dom += "}";
+        }
+        s += dom + " " + std::to_string(r.unknowns.size()) + " " + m.pool.str(r.expr) + "\n";
     }
     *out = s;
     return (int)m.residuals.size();

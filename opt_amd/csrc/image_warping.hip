@@ -2279,6 +2279,16 @@ public:
     }
 
     long long unknown_count() const override { return nvec_; }
+    int unknown_layout(int max_images, long long* offset, long long* elements, int* channels) const override {
+        const long long N = nvec_ / 3;   // Offset (2 channels), then Angle
+        const int ch[2] = {2, 1};
+        for (int k = 0; k < 2 && k < max_images; ++k) {
+            if (offset) offset[k] = k * 2 * N;
+            if (elements) elements[k] = N;
+            if (channels) channels[k] = ch[k];
+        }
+        return 2;
+    }
     std::string family() const override { return "image_warping"; }
     std::string apply_kernel_name() const override { return "iw_apply"; }
 

@@ -215,6 +215,10 @@ double Opt_ProblemCurrentCost(Opt_State* state, Opt_Plan* plan) {
 long long OptAMD_PlanUnknownCount(Opt_Plan* plan) {
     return valid_plan(plan, "OptAMD_PlanUnknownCount") ? plan->impl->unknown_count() : -1;
 }
+int OptAMD_PlanUnknownLayout(Opt_Plan* plan, int maxImages, long long* offset, long long* elements, int* channels) {
+    if (!valid_plan(plan, "OptAMD_PlanUnknownLayout")) return -1;
+    return plan->impl->unknown_layout(maxImages, offset, elements, channels);
+}
 static int copy_name(const std::string& s, char* buf, int n) {
     if (buf && n > 0) {
         strncpy(buf, s.c_str(), n - 1);

@@ -123,6 +123,9 @@ public:
         return "this energy family does not support row-slab decomposition";
     }
     virtual int halo() const { return 0; }
+    // The unknown vector's blocks (include/opt_amd.h OptAMD_PlanUnknownLayout): per unknown
+    // image its first element, its elements (pixels) and its channels; returns the image count.
+    virtual int unknown_layout(int max_images, long long* offset, long long* elements, int* channels) const = 0;
     // Materialized Jacobian (saveJToCRS, solverGPUGaussNewton.t:1004-1022): nonzeros
     // (-1: the family has no J assembly) and *rows = residual count.
     virtual long long jacobian_shape(long long* rows) const { if (rows) *rows = 0; return -1; }

@@ -195,6 +195,14 @@ public:
     std::string family() const override { return Op::kName; }
     std::string apply_kernel_name() const override { return mat_ ? mat_->apply_name() : Op::kApplyName; }
     int halo() const override { return op_->halo(); }
+    int unknown_layout(int max_images, long long* offset, long long* elements, int* channels) const override {
+        for (int k = 0; k < L_.nimg && k < max_images; ++k) {
+            if (offset) offset[k] = L_.off[k];
+            if (elements) elements[k] = (L_.off[k + 1] - L_.off[k]) / L_.ch[k];
+            if (channels) channels[k] = L_.ch[k];
+        }
+        return L_.nimg;
+    }
 
     std::string set_decomposition(Comm* comm, int y_lo, int y_hi) override {
         if (!Op::kSlabs) return std::string(Op::kName) + ": no row-slab decomposition (data-dependent reads)";
