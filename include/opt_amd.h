@@ -50,9 +50,35 @@ int OptAMD_GenericSignature(const char* filename, char* buf, int buflen);
  * (or the reference's forced value when UsePreconditioner(false)) at the current
  * unknowns; *r_dot_pre_r = sum r.(pre*r) (reference kernels.PCGInit1,
  * solverGPUGaussNewton.t:521-563, with fmap.evalJTF o.t:2870-2913). Excluded
- * elements get r = 0, pre = 0. */
+ * elements get r = 0, pre = 0. On a plan with the block preconditioner (below) pre is
+ * still this scalar preconditioner: the blocks are applied by OptAMD_ApplyPreconditioner. */
 int OptAMD_EvalJTF(Opt_State* state, Opt_Plan* plan, void** problemparams,
                    void* r, void* pre, double* r_dot_pre_r);
+
+/* Block-Jacobi preconditioner: UsePreconditioner("block") in an energy file (the reference
+ * reads any non-nil argument as true, so the file runs there with the scalar
+ * preconditioner). A block group is one index space that holds unknowns: its unknown
+ * images in problemparams order, C = the sum of their channels (at most 8, else
+ * Opt_ProblemDefine returns NULL). For element e, B_e is the C x C diagonal block of J^T J
+ * over that element's channels; PCG is preconditioned with M_e^-1, M_e = B_e on a
+ * gaussNewtonGPU plan and B_e + diag(CtC_e) (the clamped LM diagonal) on an LMGPU plan.
+ * M_e is factored by Cholesky; where a pivot is <= eps * C * max_i (M_e)_ii (eps: the
+ * machine epsilon of the solver precision) the element uses the diagonal matrix of the
+ * scalar preconditioner's values instead. Excluded elements get M_e^-1 = 0. Such energies
+ * run on generated kernels only and refuse OptAMD_PlanSetDecomposition.
+ *
+ * Writes, for each unknown image (OptAMD_PlanUnknownLayout order, up to maxImages), its
+ * block group and the row of its first channel inside the block; returns the number of
+ * groups, 0 for a plan with the scalar preconditioner, -1 for a NULL plan. */
+int OptAMD_PlanPreconditionerBlocks(Opt_Plan* plan, int maxImages, int* group, int* firstRow);
+
+/* z = M^-1 r for the caller's r (device vectors of OptAMD_PlanUnknownCount elements) with
+ * the preconditioner evaluated at the current unknowns: the GN form on a gaussNewtonGPU
+ * plan, the LM form with the plan's current trust-region radius on an LMGPU plan. On a
+ * plan with the scalar preconditioner z = pre * r. Returns 0, or 1 where the plan has no
+ * such entry point (the hand-written image_warping plan). */
+int OptAMD_ApplyPreconditioner(Opt_State* state, Opt_Plan* plan, void** problemparams,
+                               const void* r, void* z);
 
 /* Ap = J^T J p at the current unknowns (+ CtC*p for LM plans, with the CtC of the
  * last LM step) and *p_dot_Ap = p.Ap (reference kernels.PCGStep1,

@@ -61,6 +61,9 @@ _SIGNATURES = [
     ("OptAMD_EvalJTF", ctypes.c_int, [_VP, _VP, ctypes.POINTER(_VP), _VP, _VP, ctypes.POINTER(ctypes.c_double)]),
     ("OptAMD_ApplyJTJ", ctypes.c_int, [_VP, _VP, ctypes.POINTER(_VP), _VP, _VP, ctypes.POINTER(ctypes.c_double)]),
     ("OptAMD_EvalCost", ctypes.c_double, [_VP, _VP, ctypes.POINTER(_VP)]),
+    ("OptAMD_PlanPreconditionerBlocks", ctypes.c_int, [_VP, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
+                                                       ctypes.POINTER(ctypes.c_int)]),
+    ("OptAMD_ApplyPreconditioner", ctypes.c_int, [_VP, _VP, ctypes.POINTER(_VP), _VP, _VP]),
     ("OptAMD_TimeApplyJTJ", ctypes.c_double, [_VP, _VP, ctypes.POINTER(_VP), _VP, _VP, ctypes.c_int]),
     ("OptAMD_SetKernelTiming", None, [_VP, ctypes.c_int]),
     ("OptAMD_KernelStat", ctypes.c_int, [_VP, ctypes.c_char_p, ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_double)]),
@@ -282,6 +285,25 @@ class OptSolver:
             self._raise_plan_error()
             raise OptError("OptAMD_ApplyJTJ failed")
         return out.value
+
+    def preconditioner_blocks(self):
+        """(group, first_row) per unknown image and the number of block groups
+        (OptAMD_PlanPreconditionerBlocks); ([], [], 0) for a scalar preconditioner."""
+        g, fr = (ctypes.c_int * 4)(), (ctypes.c_int * 4)()
+        k = self.lib.OptAMD_PlanPreconditionerBlocks(self.plan, 4, g, fr)
+        if k < 0:
+            raise OptError("OptAMD_PlanPreconditionerBlocks failed")
+        if k == 0:
+            return [], [], 0
+        n = len(self.unknown_layout()[0])
+        return list(g)[:n], list(fr)[:n], k
+
+    def apply_preconditioner(self, problem_params, r, z) -> None:
+        """z = M^-1 r at the current unknowns (OptAMD_ApplyPreconditioner)."""
+        pk = ParamPack(problem_params)
+        if self.lib.OptAMD_ApplyPreconditioner(self.state, self.plan, pk.ptr, _ptr(r), _ptr(z)):
+            self._raise_plan_error()
+            raise OptError("OptAMD_ApplyPreconditioner failed")
 
     def eval_cost(self, problem_params) -> float:
         pk = ParamPack(problem_params)

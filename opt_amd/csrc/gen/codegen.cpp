@@ -595,6 +595,30 @@ GenSource generate(GModel& m, bool dbl, bool off32) {
     const std::string flag_lin = mspace ? "a.flags[fb + lin]" : "a.flags[lin]";
     auto in_space = [&](int image, int sp) { return !mspace || m.images[image].space == sp; };
 
+    // Block preconditioner (UsePreconditioner("block")): the kernels that build J^T F also
+    // accumulate, per element of every unknown-carrying space, the packed lower triangle of
+    // that element's diagonal block of J^T J: blk[base_g + j * N_g + e], entry j slowest.
+    const bool blockpre = m.block_preconditioner;
+    const std::vector<GBlockGroup> groups = blockpre ? m.block_groups() : std::vector<GBlockGroup>{};
+    auto group_of = [&](int sp) {
+        for (size_t g = 0; g < groups.size(); ++g)
+            if (!mspace || groups[g].space == sp) return (int)g;
+        return -1;
+    };
+    auto blk_n = [&](int g) { return mspace ? "a.snpix[" + std::to_string(groups[g].space) + "]" : std::string("a.npix"); };
+    auto blk_base = [&](int g) {
+        std::string s = "0LL";
+        for (int q = 0; q < g; ++q) s += " + " + std::to_string(groups[q].entries()) + "LL * " + blk_n(q);
+        return s;
+    };
+    auto blk_row = [&](int g, int image, int ch) {
+        for (size_t q = 0; q < groups[g].images.size(); ++q)
+            if (groups[g].images[q] == image) return groups[g].first_row[q] + ch;
+        return -1;
+    };
+    auto tri = [](int i, int j) { return i >= j ? i * (i + 1) / 2 + j : j * (j + 1) / 2 + i; };
+    const std::string blk_arg = blockpre ? ", T* __restrict__ blk" : "";
+
     // --------------------------------------------- gen_precompute_<k> (ComputedArrays)
     // One kernel per ComputedArray, launched in declaration order (a later one may read an
     // earlier one at an offset): the values and the non-constant gradient images
@@ -816,7 +840,7 @@ GenSource generate(GModel& m, bool dbl, bool off32) {
 
     // ---------------------------------------------------------------- gen_jtf
     {
-        o << "extern \"C\" __global__ __launch_bounds__(256) void gen_jtf(GenArgs a, T* __restrict__ r, T* __restrict__ diag) {\n"
+        o << "extern \"C\" __global__ __launch_bounds__(256) void gen_jtf(GenArgs a, T* __restrict__ r, T* __restrict__ diag" << blk_arg << ") {\n"
           << top_coords;
         for (int sp : uspaces) {
         o << open_space(sp);
@@ -851,6 +875,30 @@ GenSource generate(GModel& m, bool dbl, bool off32) {
                 b.line("{ const T F = " + fs + "; const T Dg = " + ds + ";");
                 b.line("  r[" + e + "] = act ? -F : (T)0; diag[" + e + "] = Dg; }");
             }
+        }
+        if (blockpre) {
+            // every pair of this element's channels: the residual instances containing both
+            const int g = group_of(sp);
+            std::vector<std::pair<int, int>> rows;   // block row -> (image, channel)
+            for (int k : groups[g].images)
+                for (int c = 0; c < m.images[k].channels; ++c) rows.push_back({k, c});
+            b.line("{ const long long bN = " + blk_n(g) + ", bB = " + blk_base(g) + ";");
+            for (int i = 0; i < groups[g].C; ++i)
+                for (int j = 0; j <= i; ++j) {
+                    std::string s = "(T)0";
+                    for (auto& e1 : inst[rows[i]])
+                        for (auto& e2 : inst[rows[j]]) {
+                            const Instance &I1 = e1.first, &I2 = e2.first;
+                            if (I1.res != I2.res || I1.s[0] != I2.s[0] || I1.s[1] != I2.s[1] || I1.s[2] != I2.s[2]) continue;
+                            const GResidual& r = m.residuals[I1.res];
+                            const int g1 = shifted(P.diff(r.expr, e1.second), I1.s), g2 = shifted(P.diff(r.expr, e2.second), I1.s);
+                            double gv;
+                            if ((P.is_const(g1, &gv) && gv == 0.0) || (P.is_const(g2, &gv) && gv == 0.0)) continue;
+                            s += " + " + b.v(g1) + " * " + b.v(g2);
+                        }
+                    b.line("  blk[bB + " + std::to_string(tri(i, j)) + "LL * bN + lin] = " + s + ";");
+                }
+            b.line("}");
         }
         o << close_space;
         }
@@ -1713,6 +1761,8 @@ GenSource generate(GModel& m, bool dbl, bool off32) {
         for (int k : unk)
             for (int c = 0; c < m.images[k].channels && in_space(k, sp); ++c)
                 o << "        T acc" << uslot[k] << "_" << c << " = 0, dg" << uslot[k] << "_" << c << " = 0;\n";
+        const int bg = blockpre && !apply ? group_of(sp) : -1;
+        for (int j = 0; bg >= 0 && j < groups[bg].entries(); ++j) o << "        T bk" << j << " = 0;\n";
         o << "        (void)0;\n";
         for (size_t g = 0; g < m.graphs.size(); ++g) {
             const size_t nslots = m.graphs[g].slot_names.size();
@@ -1749,12 +1799,18 @@ GenSource generate(GModel& m, bool dbl, bool off32) {
                     } else {
                         R = b.v(r.expr);
                     }
+                    std::vector<std::pair<std::string, int>> own;   // (partial, block row) of this vertex's unknowns
                     for (int u : mine) {
                         const int gu = P.diff(r.expr, u);
                         double gv;
                         if (P.is_const(gu, &gv) && gv == 0.0) continue;
                         const Node n = P.at(u);
                         const std::string gn = b.v(gu);
+                        if (bg >= 0) {
+                            own.push_back({gn, blk_row(bg, n.i, n.ch)});
+                            for (auto& w : own)
+                                b.line("bk" + std::to_string(tri(own.back().second, w.second)) + " += " + gn + " * " + w.first + ";");
+                        }
                         const std::string a_ = "acc" + std::to_string(uslot[n.i]) + "_" + std::to_string(n.ch);
                         const std::string d_ = "dg" + std::to_string(uslot[n.i]) + "_" + std::to_string(n.ch);
                         b.line(a_ + " += " + gn + " * " + R + ";" + (apply ? "" : " " + d_ + " += " + gn + " * " + gn + ";"));
@@ -1805,7 +1861,7 @@ GenSource generate(GModel& m, bool dbl, bool off32) {
                    "    for (long long vtx = opt_xcd_block() * 256 + threadIdx.x; vtx < a.snpix[" + s + "]; vtx += (long long)gridDim.x * 256) {\n";
         };
         const std::string flag_vtx = mspace ? "a.flags[fb + vtx]" : "a.flags[vtx]";
-        o << "extern \"C\" __global__ __launch_bounds__(256) void gen_jtf_graph(GenArgs a, T* __restrict__ r, T* __restrict__ diag) {\n"
+        o << "extern \"C\" __global__ __launch_bounds__(256) void gen_jtf_graph(GenArgs a, T* __restrict__ r, T* __restrict__ diag" << blk_arg << ") {\n"
           << top_coords;
         for (int sp : uspaces) {
         o << open_vtx(sp);
@@ -1819,6 +1875,13 @@ GenSource generate(GModel& m, bool dbl, bool off32) {
                 o << "        { const long long i = " << e << "; r[i] = act ? r[i] - acc" << sfx
                   << " : (T)0; diag[i] += dg" << sfx << "; }\n";
             }
+        if (blockpre) {
+            const int g = group_of(sp);
+            o << "        { const long long bN = " << blk_n(g) << ", bB = " << blk_base(g) << ";\n";
+            for (int j = 0; j < groups[g].entries(); ++j)
+                o << "          blk[bB + " << j << "LL * bN + vtx] += bk" << j << ";\n";
+            o << "        }\n";
+        }
         o << close_space;
         }
         o << "}\n";
@@ -1859,6 +1922,229 @@ GenSource generate(GModel& m, bool dbl, bool off32) {
         o << close_space;
         }
         o << "    double v[1] = {(double)dot};\n    block_reduce_publish<1>(v, rs, blockIdx.x);\n}\n";
+    }
+    // ------------------------------------------------ block preconditioner: PCG kernels
+    // One thread per element of a block group; every group's channel count C and the
+    // positions of its channels in the unknown vector are literals here, so the C x C
+    // Cholesky, the inversion and the products unroll into registers (packed lower triangle:
+    // C (C + 1) / 2 values per thread). gen_blk_init factors M_e = B_e (+ diag CtC_e in LM),
+    // leaves M_e^-1 in place of B_e and forms z = M^-1 r, p = z, sum r.z; gen_blk_step2 /
+    // gen_blk_half2 are PCGStep2 / the residual reset's second half (stencil_driver.h:
+    // step2_kernel, half2_kernel; the same alpha, delta, r and q expressions) with
+    // z = M_e^-1 r written to its own vector; gen_blk_apply is z = M^-1 r alone.
+    // A pivot <= eps C max_i M_ii sends the element to the diagonal matrix of the scalar
+    // preconditioner's values (w: what gn_init_kernel / lm_init_kernel left in pre);
+    // excluded elements and those outside the owned range get M^-1 = 0.
+    if (blockpre) {
+        o << "#define OPT_TRI(i, j) ((i) * ((i) + 1) / 2 + (j))\n"
+             "template <int C> __device__ __forceinline__ void opt_blk_invert(T (&m)[C * (C + 1) / 2], const T (&w)[C]) {\n"
+             "    const T eps = sizeof(T) == 8 ? (T)2.220446049250313e-16 : (T)1.1920928955078125e-07;\n"
+             "    T mx = m[0];\n"
+             "#pragma unroll\n"
+             "    for (int i = 1; i < C; ++i) mx = fmax(mx, m[OPT_TRI(i, i)]);\n"
+             "    const T tol = eps * (T)C * mx;\n"
+             "    bool ok = true;\n"
+             "#pragma unroll\n"
+             "    for (int j = 0; j < C; ++j) {   // Cholesky, L in place, its diagonal as 1 / L_jj\n"
+             "        T d = m[OPT_TRI(j, j)];\n"
+             "#pragma unroll\n"
+             "        for (int k = 0; k < j; ++k) d -= m[OPT_TRI(j, k)] * m[OPT_TRI(j, k)];\n"
+             "        ok = ok && d > tol;\n"
+             "        const T is = (T)1 / sqrt(ok ? d : (T)1);\n"
+             "        m[OPT_TRI(j, j)] = is;\n"
+             "#pragma unroll\n"
+             "        for (int i = j + 1; i < C; ++i) {\n"
+             "            T v = m[OPT_TRI(i, j)];\n"
+             "#pragma unroll\n"
+             "            for (int k = 0; k < j; ++k) v -= m[OPT_TRI(i, k)] * m[OPT_TRI(j, k)];\n"
+             "            m[OPT_TRI(i, j)] = v * is;\n"
+             "        }\n"
+             "    }\n"
+             "#pragma unroll\n"
+             "    for (int j = 0; j < C; ++j)   // L^-1 in place, column by column\n"
+             "#pragma unroll\n"
+             "        for (int i = j + 1; i < C; ++i) {\n"
+             "            T v = m[OPT_TRI(i, j)] * m[OPT_TRI(j, j)];\n"
+             "#pragma unroll\n"
+             "            for (int k = j + 1; k < i; ++k) v += m[OPT_TRI(i, k)] * m[OPT_TRI(k, j)];\n"
+             "            m[OPT_TRI(i, j)] = -v * m[OPT_TRI(i, i)];\n"
+             "        }\n"
+             "#pragma unroll\n"
+             "    for (int i = 0; i < C; ++i)   // M^-1 = L^-T L^-1 in place, row by row\n"
+             "#pragma unroll\n"
+             "        for (int j = 0; j <= i; ++j) {\n"
+             "            T v = 0;\n"
+             "#pragma unroll\n"
+             "            for (int k = i; k < C; ++k) v += m[OPT_TRI(k, i)] * m[OPT_TRI(k, j)];\n"
+             "            m[OPT_TRI(i, j)] = v;\n"
+             "        }\n"
+             "    if (!ok) {\n"
+             "#pragma unroll\n"
+             "        for (int i = 0; i < C; ++i)\n"
+             "#pragma unroll\n"
+             "            for (int j = 0; j <= i; ++j) m[OPT_TRI(i, j)] = i == j ? w[i] : (T)0;\n"
+             "    }\n"
+             "}\n"
+             "template <int C> __device__ __forceinline__ void opt_blk_mul(const T (&m)[C * (C + 1) / 2], const T (&x)[C], T (&y)[C]) {\n"
+             "#pragma unroll\n"
+             "    for (int i = 0; i < C; ++i) {\n"
+             "        T v = 0;\n"
+             "#pragma unroll\n"
+             "        for (int j = 0; j < C; ++j) v += m[i >= j ? OPT_TRI(i, j) : OPT_TRI(j, i)] * x[j];\n"
+             "        y[i] = v;\n"
+             "    }\n"
+             "}\n";
+        // per group: its literals
+        for (size_t g = 0; g < groups.size(); ++g) {
+            const GBlockGroup& G = groups[g];
+            const std::string sp = std::to_string(G.space);
+            o << "struct OptGroup" << g << " {\n    static constexpr int C = " << G.C << ";\n"
+              << "    static __device__ __forceinline__ long long n(const GenArgs& a) { return " << blk_n((int)g) << "; }\n"
+              << "    static __device__ __forceinline__ long long base(const GenArgs& a) { return " << blk_base((int)g) << "; }\n"
+              << "    static __device__ __forceinline__ bool act(const GenArgs& a, long long e) { return "
+              << (mspace ? "(a.flags[a.fbase[" + sp + "] + e] & 1) != 0" : "e >= a.own_lo && e < a.own_hi && (a.flags[e] & 1) != 0")
+              << "; }\n"
+              << "    static __device__ __forceinline__ void ix(const GenArgs& a, long long e, long long (&x)[" << G.C << "]) {\n";
+            for (size_t q = 0; q < G.images.size(); ++q) {
+                const int k = G.images[q], ch = m.images[k].channels;
+                for (int c = 0; c < ch; ++c)
+                    o << "        x[" << G.first_row[q] + c << "] = a.uoff[" << uslot[k] << "] + e * " << ch << " + " << c << ";\n";
+            }
+            o << "    }\n};\n";
+        }
+        o << "template <class G> __device__ __forceinline__ void opt_blk_load(const GenArgs& a, const T* blk, long long e, T (&m)[G::C * (G::C + 1) / 2]) {\n"
+             "    const long long bN = G::n(a), bB = G::base(a);\n"
+             "#pragma unroll\n"
+             "    for (int j = 0; j < G::C * (G::C + 1) / 2; ++j) m[j] = blk[bB + (long long)j * bN + e];\n"
+             "}\n"
+             "template <class G> __device__ __forceinline__ T opt_blk_init_group(const GenArgs& a, const T* r, const T* pre, const T* ctc, T* blk, T* z, T* p, int lm) {\n"
+             "    constexpr int C = G::C;\n"
+             "    const long long bN = G::n(a), bB = G::base(a);\n"
+             "    T acc = 0;\n"
+             "    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < bN; e += (long long)gridDim.x * 256) {\n"
+             "        long long x[C]; T m[C * (C + 1) / 2], rv[C], w[C], zv[C];\n"
+             "        G::ix(a, e, x);\n"
+             "        opt_blk_load<G>(a, blk, e, m);\n"
+             "#pragma unroll\n"
+             "        for (int i = 0; i < C; ++i) { rv[i] = r[x[i]]; w[i] = pre[x[i]]; if (lm) m[OPT_TRI(i, i)] += ctc[x[i]]; }\n"
+             "        opt_blk_invert<C>(m, w);\n"
+             "        const bool act = G::act(a, e);\n"
+             "#pragma unroll\n"
+             "        for (int j = 0; j < C * (C + 1) / 2; ++j) { m[j] = act ? m[j] : (T)0; blk[bB + (long long)j * bN + e] = m[j]; }\n"
+             "        opt_blk_mul<C>(m, rv, zv);\n"
+             "#pragma unroll\n"
+             "        for (int i = 0; i < C; ++i) { z[x[i]] = zv[i]; p[x[i]] = zv[i]; acc += rv[i] * zv[i]; }\n"
+             "    }\n"
+             "    return acc;\n"
+             "}\n"
+             "template <class G> __device__ __forceinline__ void opt_blk_step2_group(const GenArgs& a, const T* p, const T* Ap, const T* blk, const T* b, T* r, T* delta, T* z,\n"
+             "        T alpha, int first, int lm, int dl, T& acc_out, T& accq_out) {\n"
+             "    constexpr int C = G::C;\n"
+             "    const long long bN = G::n(a);\n"
+             "    T acc = 0, accq = 0;\n"
+             "    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < bN; e += (long long)gridDim.x * 256) {\n"
+             "        long long x[C]; T m[C * (C + 1) / 2], rv[C], dv[C], zv[C];\n"
+             "        G::ix(a, e, x);\n"
+             "        opt_blk_load<G>(a, blk, e, m);\n"
+             "#pragma unroll\n"
+             "        for (int i = 0; i < C; ++i) {\n"
+             "            const T rr = r[x[i]] - alpha * Ap[x[i]];\n"
+             "            T d = 0;\n"
+             "            if (dl) { d = first ? alpha * p[x[i]] : delta[x[i]] + alpha * p[x[i]]; delta[x[i]] = d; }\n"
+             "            r[x[i]] = rr; rv[i] = rr; dv[i] = d;\n"
+             "        }\n"
+             "        opt_blk_mul<C>(m, rv, zv);\n"
+             "#pragma unroll\n"
+             "        for (int i = 0; i < C; ++i) {\n"
+             "            z[x[i]] = zv[i];\n"
+             "            acc += zv[i] * rv[i];\n"
+             "            if (lm) accq += (T)0.5 * (dv[i] * (rv[i] + b[x[i]]));\n"
+             "        }\n"
+             "    }\n"
+             "    acc_out += acc; accq_out += accq;\n"
+             "}\n"
+             "template <class G> __device__ __forceinline__ void opt_blk_half2_group(const GenArgs& a, const T* Adelta, const T* b, const T* blk, const T* delta, T* r, T* z, T& acc_out, T& accq_out) {\n"
+             "    constexpr int C = G::C;\n"
+             "    const long long bN = G::n(a);\n"
+             "    T acc = 0, accq = 0;\n"
+             "    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < bN; e += (long long)gridDim.x * 256) {\n"
+             "        long long x[C]; T m[C * (C + 1) / 2], rv[C], zv[C];\n"
+             "        G::ix(a, e, x);\n"
+             "        opt_blk_load<G>(a, blk, e, m);\n"
+             "#pragma unroll\n"
+             "        for (int i = 0; i < C; ++i) { const T rr = b[x[i]] - Adelta[x[i]]; r[x[i]] = rr; rv[i] = rr; }\n"
+             "        opt_blk_mul<C>(m, rv, zv);\n"
+             "#pragma unroll\n"
+             "        for (int i = 0; i < C; ++i) {\n"
+             "            z[x[i]] = zv[i];\n"
+             "            acc += zv[i] * rv[i];\n"
+             "            accq += (T)0.5 * (delta[x[i]] * (rv[i] + b[x[i]]));\n"
+             "        }\n"
+             "    }\n"
+             "    acc_out += acc; accq_out += accq;\n"
+             "}\n"
+             "template <class G> __device__ __forceinline__ void opt_blk_apply_group(const GenArgs& a, const T* blk, const T* rin, T* zout) {\n"
+             "    constexpr int C = G::C;\n"
+             "    const long long bN = G::n(a);\n"
+             "    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < bN; e += (long long)gridDim.x * 256) {\n"
+             "        long long x[C]; T m[C * (C + 1) / 2], rv[C], zv[C];\n"
+             "        G::ix(a, e, x);\n"
+             "        opt_blk_load<G>(a, blk, e, m);\n"
+             "#pragma unroll\n"
+             "        for (int i = 0; i < C; ++i) rv[i] = rin[x[i]];\n"
+             "        opt_blk_mul<C>(m, rv, zv);\n"
+             "#pragma unroll\n"
+             "        for (int i = 0; i < C; ++i) zout[x[i]] = zv[i];\n"
+             "    }\n"
+             "}\n"
+             // LM inner-loop exit test on the launch's total q (stencil_driver.h zeta_test)
+             "__device__ __forceinline__ void opt_blk_zeta(double q1, double* q0, int* zstop, int liter, float q_tol) {\n"
+             "    const T Q1 = (T)q1, Q0 = (T)*q0;\n"
+             "    const T zeta = (T)(liter + 1) * (Q1 - Q0) / Q1;\n"
+             "    if (zeta < (T)q_tol) *zstop = 1;\n"
+             "    else *q0 = (double)Q1;\n"
+             "}\n";
+        auto each = [&](const std::string& call) {
+            std::string s;
+            for (size_t g = 0; g < groups.size(); ++g) {
+                std::string c = call;
+                c.replace(c.find("GROUP"), 5, "OptGroup" + std::to_string(g));
+                s += "    " + c + "\n";
+            }
+            return s;
+        };
+        o << "extern \"C\" __global__ __launch_bounds__(256) void gen_blk_init(GenArgs a, const T* __restrict__ r, const T* __restrict__ pre,\n"
+             "        const T* __restrict__ ctc, T* __restrict__ blk, T* __restrict__ z, T* __restrict__ p, int lm, ReduceSlot rs) {\n"
+             "    T acc = 0;\n"
+          << each("acc += opt_blk_init_group<GROUP>(a, r, pre, ctc, blk, z, p, lm);")
+          << "    double v[1] = {(double)acc};\n    block_reduce_publish<1>(v, rs, blockIdx.x);\n}\n";
+        o << "extern \"C\" __global__ __launch_bounds__(256) void gen_blk_step2(GenArgs a, const T* __restrict__ p, const T* __restrict__ Ap,\n"
+             "        const T* __restrict__ blk, const T* __restrict__ b, T* __restrict__ r, T* __restrict__ delta, T* __restrict__ z,\n"
+             "        const double* __restrict__ sc, int i_num, int i_den, int first, int lm, int dl, const int* stop, ReduceSlot rs,\n"
+             "        double* q0, int* zstop, int liter, float q_tol, int zon) {\n"
+             "    if (stop && *stop) return;\n"
+             "    const T alpha = (T)(sc[i_num] / sc[i_den]);\n"
+             "    T acc = 0, accq = 0;\n"
+          << each("opt_blk_step2_group<GROUP>(a, p, Ap, blk, b, r, delta, z, alpha, first, lm, dl, acc, accq);")
+          << "    double v[2] = {(double)acc, (double)accq};\n"
+             "    if (lm) {\n"
+             "        double tot[2];\n"
+             "        if (block_reduce_publish<2>(v, rs, blockIdx.x, tot) && zon) opt_blk_zeta(tot[1], q0, zstop, liter, q_tol);\n"
+             "    } else {\n"
+             "        double v1[1] = {v[0]};\n"
+             "        block_reduce_publish<1>(v1, rs, blockIdx.x);\n"
+             "    }\n}\n";
+        o << "extern \"C\" __global__ __launch_bounds__(256) void gen_blk_half2(GenArgs a, const T* __restrict__ Adelta, const T* __restrict__ b,\n"
+             "        const T* __restrict__ blk, const T* __restrict__ delta, T* __restrict__ r, T* __restrict__ z, const int* stop, ReduceSlot rs,\n"
+             "        double* q0, int* zstop, int liter, float q_tol, int zon) {\n"
+             "    if (stop && *stop) return;\n"
+             "    T acc = 0, accq = 0;\n"
+          << each("opt_blk_half2_group<GROUP>(a, Adelta, b, blk, delta, r, z, acc, accq);")
+          << "    double v[2] = {(double)acc, (double)accq};\n"
+             "    double tot[2];\n"
+             "    if (block_reduce_publish<2>(v, rs, blockIdx.x, tot) && zon) opt_blk_zeta(tot[1], q0, zstop, liter, q_tol);\n}\n";
+        o << "extern \"C\" __global__ __launch_bounds__(256) void gen_blk_apply(GenArgs a, const T* __restrict__ blk, const T* __restrict__ rin, T* __restrict__ zout) {\n"
+          << each("opt_blk_apply_group<GROUP>(a, blk, rin, zout);") << "}\n";
     }
     (void)zero3;
     g_cache = nullptr;

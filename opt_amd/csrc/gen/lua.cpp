@@ -1259,6 +1259,8 @@ void Interp::install() {
     });
     def("UsePreconditioner", [this](VList& a) {
         m_->use_preconditioner = !a.empty() && truthy(a[0]);
+        // "block": the block-Jacobi form (any other non-nil argument is the reference's true)
+        m_->block_preconditioner = !a.empty() && a[0].k == V::Str && a[0].s == "block";
         return VList{};
     });
     def("Exclude", [this](VList& a) {
@@ -1687,6 +1689,21 @@ std::vector<int> GModel::unknown_spaces() const {
     std::vector<int> out;
     for (int k : unknown_images())
         if (std::find(out.begin(), out.end(), images[k].space) == out.end()) out.push_back(images[k].space);
+    return out;
+}
+std::vector<GBlockGroup> GModel::block_groups() const {
+    std::vector<GBlockGroup> out;
+    for (int sp : unknown_spaces()) {
+        GBlockGroup g;
+        g.space = sp;
+        for (int k : unknown_images())
+            if (images[k].space == sp) {
+                g.images.push_back(k);
+                g.first_row.push_back(g.C);
+                g.C += images[k].channels;
+            }
+        out.push_back(g);
+    }
     return out;
 }
 std::vector<int> GModel::unknown_images() const {

@@ -56,6 +56,16 @@ struct GResidual {
     int space = -1;                // centred: the index space it is instantiated over
 };
 
+// A block group of the block preconditioner: one index space that holds unknowns; its
+// unknown images in problemparams order, each with the block row of its first channel.
+struct GBlockGroup {
+    int space = -1;
+    int C = 0;                     // channels of all its unknown images
+    std::vector<int> images;       // image ids
+    std::vector<int> first_row;    // per image: row of its channel 0 inside the C x C block
+    int entries() const { return C * (C + 1) / 2; }   // packed lower triangle
+};
+
 struct GModel {
     Pool pool;
     std::vector<GDim> dims;
@@ -73,6 +83,9 @@ struct GModel {
     std::vector<std::vector<int>> spaces;
     std::vector<std::pair<int, int>> excludes;   // (space, expr): at most one Exclude per space
     bool use_preconditioner = false;
+    // UsePreconditioner("block"): PCG preconditioned with the inverse of each element's
+    // diagonal block of J^T J over all unknown channels of its index space
+    bool block_preconditioner = false;
     std::string unsupported;       // first construct the generic path cannot lower
     int n_params_total = 0;
 
@@ -82,6 +95,7 @@ struct GModel {
     int exclude_of(int space) const;                     // Exclude expression of a space, -1 = none
     std::vector<int> unknown_spaces() const;             // spaces holding unknowns, in unknown_images() order
     std::vector<int> unknown_images() const;   // image ids of the unknowns, declaration order
+    std::vector<GBlockGroup> block_groups() const;       // in unknown_spaces() order
 };
 
 // Run `text` (an Opt energy file). false + message on a Lua or DSL error.

@@ -135,8 +135,18 @@ bool generic_accepts(const std::string& text, ProblemSpec* spec, std::string* er
     for (auto& sp : m.spaces)
         if (sp.size() < 1 || sp.size() > 3) { *err = "index spaces must be 1-, 2- or 3-dimensional"; return false; }
     if (m.residuals.empty()) { *err = "no Energy terms"; return false; }
+    if (m.block_preconditioner)
+        for (auto& g : m.block_groups())
+            if (g.C > 8) {
+                std::string sn = "{";
+                for (size_t k = 0; k < m.spaces[g.space].size(); ++k) sn += (k ? "," : "") + m.dims[m.spaces[g.space][k]].name;
+                *err = "UsePreconditioner(\"block\"): index space " + sn + "} holds " + std::to_string(g.C) +
+                       " unknown channels (a block has at most 8)";
+                return false;
+            }
     spec->text = text;
     spec->use_preconditioner = m.use_preconditioner;
+    spec->block_preconditioner = m.block_preconditioner;
     spec->family = "generic";
     return true;
 }
@@ -183,6 +193,8 @@ bool generic_signature(const std::string& text, std::string* sig, bool* use_pre,
     for (auto& r : m.residuals)
         s += "R" + std::to_string(r.graph) + (m.multi() && r.graph < 0 ? "s" + std::to_string(r.space) : "") + ":" +
              std::to_string(r.unknowns.size()) + ":" + m.pool.str(r.expr) + ";";
+    // (only when requested: every other energy's signature is what it always was)
+    if (m.block_preconditioner) s += "B;";
     *sig = s;
     if (use_pre) *use_pre = m.use_preconditioner;
     return true;
@@ -242,6 +254,7 @@ public:
             exit(1);
         }
         unk_ = m_.unknown_images();
+        if (m_.block_preconditioner) groups_ = m_.block_groups();
         const gen::GImage& u0 = m_.images[unk_[0]];
         dims_[0] = dims_[1] = dims_[2] = 1;
         for (size_t k = 0; k < u0.dims.size(); ++k) dims_[k] = (int)spec.dim_values.at(m_.dims[u0.dims[k]].index);
@@ -331,6 +344,9 @@ public:
     // Why this energy cannot run on row slabs ("" = it can). Graph and sampled reads are
     // data-dependent (as the optical_flow / ARAP families), slabs split the 2nd dimension.
     std::string slab_refusal() const {
+        // (a halo element's z needs its neighbours' blocks: a change of its own)
+        if (m_.block_preconditioner)
+            return "generic: no row-slab decomposition with the block preconditioner (UsePreconditioner(\"block\"))";
         if (multi_) return "generic: no row-slab decomposition for an energy over several index spaces";
         if (m_.unknown_dims() != 2) return "generic: row-slab decomposition needs a 2-D energy";
         if (!m_.graphs.empty()) return "generic: no row-slab decomposition for graph energies";
@@ -449,9 +465,51 @@ public:
 
     void jtf(T* r, T* diag, uint8_t* flags, hipStream_t s) {
         a_.flags = flags;
+        if (m_.block_preconditioner) {   // the same kernels with the blocks' triangle beside diag
+            launch(k_jtf_, s, {&a_, &r, &diag, &blk_});
+            if (src_.has_graph) launch(k_jtf_graph_, s, {&a_, &r, &diag, &blk_});
+            return;
+        }
         launch(k_jtf_, s, {&a_, &r, &diag});   // flags, and r / diag of the centred residuals
         if (src_.has_graph) launch(k_jtf_graph_, s, {&a_, &r, &diag});
     }
+
+    // ---- block preconditioner (UsePreconditioner("block"); StencilPlan: HasBlockPre) ----
+    // The plan owns the buffers: blk (block_entries() values: every group's packed lower
+    // triangles, entry index slowest) is filled by jtf next to diag, factored and inverted in
+    // place by block_init, and read by the other kernels; z is PCG's z = M^-1 r.
+    bool block_pre() const { return m_.block_preconditioner; }
+    long long block_entries() const {
+        long long n = 0;
+        for (auto& g : groups_) n += (long long)g.entries() * pixels_of(g.images[0]);
+        return n;
+    }
+    void set_block_buffer(T* blk) { blk_ = blk; }
+    // per unknown image (VecLayout order): its group and the block row of its first channel
+    int block_layout(int max_images, int* group, int* first_row) const {
+        for (size_t k = 0; k < unk_.size() && (int)k < max_images; ++k)
+            for (size_t g = 0; g < groups_.size(); ++g)
+                for (size_t q = 0; q < groups_[g].images.size(); ++q)
+                    if (groups_[g].images[q] == unk_[k]) {
+                        if (group) group[k] = (int)g;
+                        if (first_row) first_row[k] = groups_[g].first_row[q];
+                    }
+        return (int)groups_.size();
+    }
+    void block_init(const T* r, const T* pre, const T* ctc, T* z, T* p, int lm, ReduceSlot rs, hipStream_t s) {
+        launch(k_blk_init_, s, {&a_, &r, &pre, &ctc, &blk_, &z, &p, &lm, &rs});
+    }
+    void block_step2(const T* p, const T* Ap, const T* b, T* r, T* delta, T* z, const double* sc, int i_num, int i_den,
+                     int first, int lm, int dl, const int* stop, ReduceSlot rs, ZetaArgs zt, hipStream_t s) {
+        launch(k_blk_step2_, s, {&a_, &p, &Ap, &blk_, &b, &r, &delta, &z, &sc, &i_num, &i_den, &first, &lm, &dl, &stop, &rs,
+                                 &zt.q0, &zt.stop, &zt.liter, &zt.q_tol, &zt.on});
+    }
+    void block_half2(const T* Adelta, const T* b, const T* delta, T* r, T* z, const int* stop, ReduceSlot rs, ZetaArgs zt,
+                     hipStream_t s) {
+        launch(k_blk_half2_, s, {&a_, &Adelta, &b, &blk_, &delta, &r, &z, &stop, &rs, &zt.q0, &zt.stop, &zt.liter, &zt.q_tol,
+                                 &zt.on});
+    }
+    void block_apply(const T* rin, T* zout, hipStream_t s) { launch(k_blk_apply_, s, {&a_, &blk_, &rin, &zout}); }
     void apply(const T* p, T* Ap, const T* dadd, const int* stop, ReduceSlot rs, hipStream_t s) {
         if (!src_.has_graph) {
             int finish = 1;
@@ -587,7 +645,13 @@ private:
             if (per_cu > 0 && cus > 0) max_blocks_ = std::min(4096, std::max(8, per_cu * cus));
         }
         // J^T F: the register strip under the same rule (OPT_AMD_GEN_JTF=gather|strip forces)
-        if (src_.has_jtf_strip && !slab) {
+        if (m_.block_preconditioner) {
+            for (auto kv : {std::make_pair(&k_blk_init_, "gen_blk_init"), std::make_pair(&k_blk_step2_, "gen_blk_step2"),
+                            std::make_pair(&k_blk_half2_, "gen_blk_half2"), std::make_pair(&k_blk_apply_, "gen_blk_apply")})
+                OPT_HIP_CHECK(hipModuleGetFunction(kv.first, mod_, kv.second));
+        }
+        // (the strip J^T F has no block accumulation: block energies keep the gather)
+        if (src_.has_jtf_strip && !slab && !m_.block_preconditioner) {
             const char* wj = getenv("OPT_AMD_GEN_JTF");
             const std::string fj = wj ? wj : "";
             const long long waves = (long long)((dims_[0] + src_.jtf_strip_cols - 1) / src_.jtf_strip_cols) * ((dims_[1] + 7) / 8);
@@ -728,6 +792,9 @@ private:
     std::vector<hipFunction_t> k_pre_, k_dump_;
     hipFunction_t k_apply_tiled_{}, k_apply_strip_{};
     hipFunction_t k_jtf_{}, k_apply_{}, k_cost_{}, k_jtf_graph_{}, k_apply_graph_{};
+    hipFunction_t k_blk_init_{}, k_blk_step2_{}, k_blk_half2_{}, k_blk_apply_{};
+    std::vector<gen::GBlockGroup> groups_;   // block preconditioner: empty without it
+    T* blk_ = nullptr;                       // the plan's block buffer (set_block_buffer)
 };
 
 std::unique_ptr<Plan> make_generic_plan(const ProblemSpec& spec, const StateOptions& opts, const unsigned* dims,

@@ -241,6 +241,15 @@ int OptAMD_EvalJTF(Opt_State* state, Opt_Plan* plan, void** params, void* r, voi
     if (rz) *rz = t;
     return e;
 }
+int OptAMD_PlanPreconditionerBlocks(Opt_Plan* plan, int maxImages, int* group, int* firstRow) {
+    if (!valid_plan(plan, "OptAMD_PlanPreconditionerBlocks")) return -1;
+    return plan->impl->preconditioner_blocks(maxImages, group, firstRow);
+}
+int OptAMD_ApplyPreconditioner(Opt_State* state, Opt_Plan* plan, void** params, const void* r, void* z) {
+    if (!valid_state(state, "OptAMD_ApplyPreconditioner") || !valid_plan(plan, "OptAMD_ApplyPreconditioner") || !r || !z)
+        return 1;
+    return guarded(plan, "OptAMD_ApplyPreconditioner", 1, [&] { return plan->impl->apply_preconditioner(params, r, z); });
+}
 int OptAMD_ApplyJTJ(Opt_State* state, Opt_Plan* plan, void** params, const void* p, void* Ap,
                     double* pAp) {
     if (!valid_state(state, "OptAMD_ApplyJTJ") || !valid_plan(plan, "OptAMD_ApplyJTJ") || !p || !Ap)

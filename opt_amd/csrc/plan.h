@@ -141,6 +141,19 @@ public:
         return 1;
     }
 
+    // Block preconditioner (include/opt_amd.h): per unknown image its block group and the row
+    // of its first channel inside the block; the number of groups, 0 for a scalar plan.
+    virtual int preconditioner_blocks(int max_images, int* group, int* first_row) const {
+        (void)max_images; (void)group; (void)first_row;
+        return 0;
+    }
+    // z = M^-1 r at the current unknowns (device vectors of unknown_count() elements);
+    // 1 where the plan has no such entry point.
+    virtual int apply_preconditioner(void** params, const void* r, void* z) {
+        (void)params; (void)r; (void)z;
+        return 1;
+    }
+
     void set_solver_param(const char* name, const void* value);
     // the device scalar slots (red_.scalars) to the host, up to n; the count copied
     int scalars(double* out, int n);

@@ -260,6 +260,11 @@ struct Parser {
                 args(i + 1, &a);
                 if (a.size() == 1 && is_single(a[0], Tk::Name))
                     spec->use_preconditioner = (t[a[0].first].text == "true");
+                // "block": on (the reference takes any non-nil argument as true), block form
+                if (a.size() == 1 && is_single(a[0], Tk::String)) {
+                    spec->use_preconditioner = true;
+                    spec->block_preconditioner = (t[a[0].first].text == "block");
+                }
             } else if (f == "Exclude") {
                 spec->n_exclude++;
             } else if (f == "ComputedArray") {

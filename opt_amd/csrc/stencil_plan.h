@@ -174,6 +174,24 @@ template <class Op>
 struct HasCaptureKey<Op, std::void_t<decltype(std::declval<const Op&>().capture_key(
                              (std::vector<unsigned long long>*)nullptr))>> : std::true_type {};
 
+// Ops with a block preconditioner (GenericOp for UsePreconditioner("block")): block_pre()
+// says whether this energy asked for it; then jtf also fills the plan's block buffer
+// (set_block_buffer, block_entries() values) and block_init / block_step2 / block_half2 /
+// block_apply are the per-element PCG kernels that replace the scalar z = pre r: z goes to
+// its own vector, and PCGStep3 runs on it with use_pre = 0.
+template <class Op, class = void>
+struct HasBlockPre : std::false_type {};
+template <class Op>
+struct HasBlockPre<Op, std::void_t<decltype(std::declval<const Op&>().block_pre())>> : std::true_type {};
+
+// z = pre r (OptAMD_ApplyPreconditioner on a scalar plan)
+template <typename T>
+__global__ __launch_bounds__(kBlock) void scale_kernel(long long n, const T* __restrict__ pre, const T* __restrict__ r,
+                                                       T* __restrict__ z) {
+    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x)
+        z[e] = pre[e] * r[e];
+}
+
 template <class Op>
 class StencilPlan final : public Plan {
 public:
@@ -284,6 +302,12 @@ public:
             OPT_HIP_CHECK(hipMemsetAsync(red_.scalars + kScQ0, 0, sizeof(double), stream_));
         }
         OPT_HIP_CHECK(hipGetLastError());
+        if constexpr (HasBlockPre<Op>::value)
+            if (block_) {   // M_e^-1 in place of the blocks, z_0 = M^-1 r, p_0 = z_0, rz_0
+                tbegin("blk_init");
+                op_->block_init(r_, pre_, CtC_, z_, p_, lm_ ? 1 : 0, red_.slot(nb(), rz(0)), stream_);
+                tend();
+            }
         allreduce(rz(0), 1);
         const int* stop = lm_ ? stop_ : nullptr;
         if (mat_) materialize();   // cusparseOuter (:2068): J, J^T (, J^T J) at the current X
@@ -370,17 +394,49 @@ public:
                                    delta_, red_.scalars, rz(i), pap(i), stop);
                 exchange_vec(delta_);
                 op_->apply(delta_, Adelta_, CtC_, stop, red_.slot(nb(), kScTmp), stream_);
+                bool blk = false;
+                if constexpr (HasBlockPre<Op>::value)
+                    if (block_) {
+                        tbegin("blk_half2");
+                        op_->block_half2(Adelta_, b_, delta_, r_, z_, stop, red_.slot(nb(), rz(i + 1)), z, stream_);
+                        tend();
+                        blk = true;
+                    }
+                if (!blk)
                 hipLaunchKernelGGL((half2_kernel<T>), dim3(fg()), dim3(kBlock), 0, stream_, n_, (const T*)Adelta_,
                                    (const T*)b_, (const T*)pre_, (const T*)delta_, r_, use_pre, stop,
                                    red_.slot(fg(), rz(i + 1)), z);
             } else {
+                bool blk = false;
+                if constexpr (HasBlockPre<Op>::value)
+                    if (block_) {
+                        tbegin("blk_step2");
+                        op_->block_step2(p_, Ap_, b_, r_, delta_, z_, red_.scalars, rz(i), pap(i), i == 0 ? 1 : 0,
+                                         lm_ ? 1 : 0, (lm_ || !d3) ? 1 : 0, stop, red_.slot(nb(), rz(i + 1)), z, stream_);
+                        tend();
+                        blk = true;
+                    }
+                if (!blk) {
                 tbegin("step2");
                 launch_step2(i == 0, rz(i), pap(i), rz(i + 1), stop, z, !d3);
                 tend();
+                }
             }
             allreduce(rz(i + 1), lm_ ? 2 : 1);   // rz and q sit side by side
             tbegin("step3");
             bool fused = false;
+            if (block_) {   // p = z + beta p on the block path's z (step3_kernel's r), no pre
+                if (d3 && i == 0)
+                    hipLaunchKernelGGL((step3_kernel<T, 1>), dim3(fg()), dim3(kBlock), 0, stream_, n_, (const T*)pre_,
+                                       (const T*)z_, p_, red_.scalars, rz(i + 1), rz(i), 0, stop, delta_, rz(i), pap(i));
+                else if (d3)
+                    hipLaunchKernelGGL((step3_kernel<T, 2>), dim3(fg()), dim3(kBlock), 0, stream_, n_, (const T*)pre_,
+                                       (const T*)z_, p_, red_.scalars, rz(i + 1), rz(i), 0, stop, delta_, rz(i), pap(i));
+                else
+                    hipLaunchKernelGGL((step3_kernel<T>), dim3(fg()), dim3(kBlock), 0, stream_, n_, (const T*)pre_,
+                                       (const T*)z_, p_, red_.scalars, rz(i + 1), rz(i), 0, stop);
+                fused = true;
+            }
             if constexpr (HasFusedStep3<Op>::value)
                 if (fuse3) {
                     op_->step3_fused(pre_, r_, p_, red_.scalars, rz(i + 1), rz(i), use_pre, stop, stream_);
@@ -504,6 +560,10 @@ public:
                                             (unsigned long long)(uintptr_t)op_.get(),
                                             (unsigned long long)(uintptr_t)p_};
         key.insert(key.end(), op_key.begin(), op_key.end());
+        if (block_) {   // the block path's launches also bake in its two buffers
+            key.push_back((unsigned long long)(uintptr_t)blk_);
+            key.push_back((unsigned long long)(uintptr_t)z_);
+        }
         if constexpr (!HasCaptureKey<Op>::value) {
             for (const DeclImage& im : spec_.images)   // arrays by address, scalars by value (below)
                 if (im.index >= 0 && im.index < spec_.n_params_total)
@@ -613,6 +673,51 @@ public:
         end_call();
         return 0;
     }
+    // z = M^-1 r at the current unknowns for the caller's r: the GN form on a GN plan, the LM
+    // form with the current trust-region radius on an LM plan (the scalar init kernels run as
+    // in step(); every buffer they write is rebuilt by the next step).
+    int apply_preconditioner(void** params, const void* rin, void* zout) override {
+        begin_call();
+        prepare(params);
+        const int use_pre = spec_.use_preconditioner ? 1 : 0;
+        const long long lo = pix_lo(), hi = pix_hi();
+        red_.ensure(std::max(op_->stencil_blocks(), 4096), 4, kScBase + kSlots * (std::max(0, sp_.lIterations) + 2));
+        op_->jtf(r_, diag_, flags_, stream_);
+        exchange({{(void*)flags_, (size_t)dom_.W}});
+        if (!lm_) {
+            hipLaunchKernelGGL((gn_init_kernel<T>), dim3(fg()), dim3(kBlock), 0, stream_, L_, (const uint8_t*)flags_,
+                               r_, (const T*)diag_, pre_, p_, use_pre, lo, hi, red_.slot(fg(), kScTmp));
+        } else {
+            LMScalars lm{initialised_ ? radius_ : sp_.trust_region_radius, sp_.min_lm_diagonal, sp_.max_lm_diagonal};
+            if (!initialised_ || n_iter_ == 0)
+                hipLaunchKernelGGL((lm_init_kernel<T, true>), dim3(fg()), dim3(kBlock), 0, stream_, L_,
+                                   (const uint8_t*)flags_, r_, (const T*)diag_, SSq_, CtC_, pre_, b_, p_,
+                                   use_pre, lm, lo, hi, red_.slot(fg(), kScTmp));
+            else
+                hipLaunchKernelGGL((lm_init_kernel<T, false>), dim3(fg()), dim3(kBlock), 0, stream_, L_,
+                                   (const uint8_t*)flags_, r_, (const T*)diag_, SSq_, CtC_, pre_, b_, p_,
+                                   use_pre, lm, lo, hi, red_.slot(fg(), kScTmp));
+        }
+        OPT_HIP_CHECK(hipGetLastError());
+        bool blk = false;
+        if constexpr (HasBlockPre<Op>::value)
+            if (block_) {
+                op_->block_init(r_, pre_, CtC_, z_, p_, lm_ ? 1 : 0, red_.slot(nb(), kScTmp), stream_);
+                op_->block_apply((const T*)rin, (T*)zout, stream_);
+                blk = true;
+            }
+        if (!blk)
+            hipLaunchKernelGGL((scale_kernel<T>), dim3(fg()), dim3(kBlock), 0, stream_, n_, (const T*)pre_,
+                               (const T*)rin, (T*)zout);
+        OPT_HIP_CHECK(hipGetLastError());
+        end_call();
+        return 0;
+    }
+    int preconditioner_blocks(int max_images, int* group, int* first_row) const override {
+        if constexpr (HasBlockPre<Op>::value)
+            if (block_) return op_->block_layout(max_images, group, first_row);
+        return 0;
+    }
     int apply_jtj(void** params, const void* p, void* Ap, double* pAp) override {
         begin_call();
         prepare(params);
@@ -718,6 +823,17 @@ private:
                 *v = (T*)dmalloc(sizeof(T) * n_);
         for (T* v : {r_, diag_, pre_, p_, Ap_, delta_, b_, CtC_, SSq_, prev_, Adelta_})
             if (v) OPT_HIP_CHECK(hipMemset(v, 0, sizeof(T) * n_));
+        if constexpr (HasBlockPre<Op>::value) {
+            block_ = op_->block_pre();
+            if (block_) {
+                const long long nb = op_->block_entries();
+                blk_ = (T*)dmalloc(sizeof(T) * nb);
+                z_ = (T*)dmalloc(sizeof(T) * n_);
+                OPT_HIP_CHECK(hipMemset(blk_, 0, sizeof(T) * nb));
+                OPT_HIP_CHECK(hipMemset(z_, 0, sizeof(T) * n_));
+                op_->set_block_buffer(blk_);
+            }
+        }
         flags_ = (uint8_t*)dmalloc(dom_.npix_mem());
         OPT_HIP_CHECK(hipMemset(flags_, 0, dom_.npix_mem()));
         red_.ensure(std::max(op_->stencil_blocks(), 4096), 2, 64);
@@ -729,7 +845,7 @@ private:
     }
     void release() {
         drop_graph();
-        for (T** v : {&r_, &diag_, &pre_, &p_, &Ap_, &delta_, &b_, &CtC_, &SSq_, &prev_, &Adelta_}) {
+        for (T** v : {&r_, &diag_, &pre_, &p_, &Ap_, &delta_, &b_, &CtC_, &SSq_, &prev_, &Adelta_, &blk_, &z_}) {
             dfree(*v);
             *v = nullptr;
         }
@@ -850,6 +966,8 @@ private:
     long long n_ = 0;
     T *r_ = nullptr, *diag_ = nullptr, *pre_ = nullptr, *p_ = nullptr, *Ap_ = nullptr, *delta_ = nullptr;
     T *b_ = nullptr, *CtC_ = nullptr, *SSq_ = nullptr, *prev_ = nullptr, *Adelta_ = nullptr;
+    bool block_ = false;                       // block preconditioner (HasBlockPre)
+    T *blk_ = nullptr, *z_ = nullptr;          // its blocks (inverted in place) and z = M^-1 r
     uint8_t* flags_ = nullptr;
     int* stop_ = nullptr;
     hipGraphExec_t graph_exec_ = nullptr;      // captured PCG loop (pcg_graph_begin)
