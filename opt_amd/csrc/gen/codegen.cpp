@@ -37,7 +37,9 @@ namespace gen {
 namespace {
 
 std::string lit(double v) {
-    if (std::isinf(v)) return v < 0 ? "(-(T)HUGE_VAL)" : "((T)HUGE_VAL)";
+    // (builtins: the runtime compiler's headers define neither HUGE_VAL nor NAN)
+    if (std::isinf(v)) return v < 0 ? "(-(T)__builtin_huge_val())" : "((T)__builtin_huge_val())";
+    if (std::isnan(v)) return "((T)__builtin_nan(\"\"))";
     char b[64];
     snprintf(b, sizeof(b), "%.17g", v);
     std::string s = b;
@@ -114,7 +116,12 @@ int g_widu = 2;
 bool g_factor = true;
 
 bool transcendental(const Node& n) {
-    return n.op == Op::Sin || n.op == Op::Cos || n.op == Op::Exp || n.op == Op::Log || n.op == Op::Sqrt;
+    switch (n.op) {
+        case Op::Sin: case Op::Cos: case Op::Exp: case Op::Log: case Op::Sqrt:
+        case Op::Tan: case Op::Tanh: case Op::Sinh: case Op::Cosh: case Op::Asin: case Op::Acos:
+        case Op::Atan: case Op::Asinh: case Op::Acosh: case Op::Log10: return true;
+        default: return false;
+    }
 }
 bool cacheable(const Pool& P, const Node& n) {
     if (!transcendental(n)) return false;
@@ -202,7 +209,7 @@ public:
             auto ci = g_cache->find(std::make_tuple((int)n.op, c.i, c.ch));
             if (ci != g_cache->end()) {
                 // outside the image the argument reads 0: f(0), as the evaluated form
-                const double f0 = n.op == Op::Cos || n.op == Op::Exp ? 1.0 : n.op == Op::Log ? -HUGE_VAL : 0.0;
+                const double f0 = fold1(n.op, 0.0);
                 const std::string name = "k" + std::to_string(id);
                 o_ << "        const T " << name << " = (" << inb(c.off) << ") ? ((const T*)a.img[" << ci->second
                    << "])[li + " << rel(c.off) << "] : " << lit(f0) << ";\n";
@@ -244,6 +251,18 @@ public:
             case Op::Log: e = "log(" + v(n.a) + ")"; break;
             case Op::Abs: e = "fabs(" + v(n.a) + ")"; break;
             case Op::Pow: e = "pow(" + v(n.a) + ", " + v(n.b) + ")"; break;
+            // overloaded on T: the float module calls the float versions
+            case Op::Tan: e = "tan(" + v(n.a) + ")"; break;
+            case Op::Tanh: e = "tanh(" + v(n.a) + ")"; break;
+            case Op::Sinh: e = "sinh(" + v(n.a) + ")"; break;
+            case Op::Cosh: e = "cosh(" + v(n.a) + ")"; break;
+            case Op::Asin: e = "asin(" + v(n.a) + ")"; break;
+            case Op::Acos: e = "acos(" + v(n.a) + ")"; break;
+            case Op::Atan: e = "atan(" + v(n.a) + ")"; break;
+            case Op::Asinh: e = "asinh(" + v(n.a) + ")"; break;
+            case Op::Acosh: e = "acosh(" + v(n.a) + ")"; break;
+            case Op::Log10: e = "log10(" + v(n.a) + ")"; break;
+            case Op::Atan2: e = "atan2(" + v(n.a) + ", " + v(n.b) + ")"; break;
             case Op::Select: e = cond(n.a) + " ? " + v(n.b) + " : " + v(n.d); break;
             case Op::Sample:
                 e = "opt_sample(" + img_ptr(n.i) + ", " + std::to_string(M_.images[n.i].channels) + ", " +
@@ -645,9 +664,9 @@ GenSource generate(GModel& m, bool dbl, bool off32) {
 
     // ------------------------------------------------ transcendental caches (see g_cache)
     // Worth it when residuals have instances at several shifts (each would re-evaluate
-    // its neighbours' transcendentals): cache every sin / cos / exp / log / sqrt of a
-    // centred read the residuals use, one internal image each, filled by one extra
-    // precompute kernel after the ComputedArrays.
+    // its neighbours' transcendentals): cache every sin / cos / exp / log / sqrt / tan /
+    // atan / ... (transcendental()) of a centred read the residuals use, one internal image
+    // each, filled by one extra precompute kernel after the ComputedArrays.
     CacheMap cache;
     {
         bool multi = false;
@@ -1153,7 +1172,10 @@ GenSource generate(GModel& m, bool dbl, bool off32) {
                 // de, 0), 0): its mask is evaluated once (m<ci>) and applied to Jp alone — each
                 // partial's contribution d * Jp is then 0 with it — instead of a select per
                 // partial; only when every partial is free of operations that can be non-finite
-                // where the mask is off (division, sqrt, log, pow, exp), where 0 * d could be NaN.
+                // where the mask is off (division, sqrt, log, pow, exp; tan, sinh, cosh, asin,
+                // acos, acosh, log10: out of domain or overflowing on whatever the masked data
+                // holds), where 0 * d could be NaN. atan, tanh, asinh and atan2 are finite for
+                // every finite input (and their partials hold a division anyway).
                 std::vector<int> conds;
                 std::vector<int> de(ents.size(), -1);
                 bool factor = !jtf && g_factor;
@@ -1175,7 +1197,10 @@ GenSource generate(GModel& m, bool dbl, bool off32) {
                         }
                         P.visit(x, [&](int, const Node& n) {
                             factor = factor && n.op != Op::Div && n.op != Op::Sqrt && n.op != Op::Log &&
-                                     n.op != Op::Pow && n.op != Op::Exp && n.op != Op::Sample;
+                                     n.op != Op::Pow && n.op != Op::Exp && n.op != Op::Sample &&
+                                     n.op != Op::Tan && n.op != Op::Sinh && n.op != Op::Cosh &&
+                                     n.op != Op::Asin && n.op != Op::Acos && n.op != Op::Acosh &&
+                                     n.op != Op::Log10;
                         });
                         de[ei] = x;
                     }

@@ -69,7 +69,7 @@ int Pool::coord(int dim, int off) {
     return intern(n);
 }
 
-static double fold1(Op op, double a) {
+double fold1(Op op, double a) {
     switch (op) {
         case Op::Neg: return -a;
         case Op::Sqrt: return std::sqrt(a);
@@ -79,10 +79,20 @@ static double fold1(Op op, double a) {
         case Op::Log: return std::log(a);
         case Op::Abs: return std::fabs(a);
         case Op::Not: return a == 0.0 ? 1.0 : 0.0;
+        case Op::Tan: return std::tan(a);
+        case Op::Tanh: return std::tanh(a);
+        case Op::Sinh: return std::sinh(a);
+        case Op::Cosh: return std::cosh(a);
+        case Op::Asin: return std::asin(a);
+        case Op::Acos: return std::acos(a);
+        case Op::Atan: return std::atan(a);
+        case Op::Asinh: return std::asinh(a);
+        case Op::Acosh: return std::acosh(a);
+        case Op::Log10: return std::log10(a);
         default: return 0.0;
     }
 }
-static double fold2(Op op, double a, double b) {
+double fold2(Op op, double a, double b) {
     switch (op) {
         case Op::Add: return a + b;
         case Op::Sub: return a - b;
@@ -97,6 +107,7 @@ static double fold2(Op op, double a, double b) {
         case Op::Ne: return a != b;
         case Op::And: return (a != 0.0 && b != 0.0) ? 1.0 : 0.0;
         case Op::Or: return (a != 0.0 || b != 0.0) ? 1.0 : 0.0;
+        case Op::Atan2: return std::atan2(a, b);
         default: return 0.0;
     }
 }
@@ -244,6 +255,40 @@ int Pool::diff(int id, int var) {
                             bin(Op::Div, bin(Op::Mul, n.b, diff(n.a, var)), n.a)));
             break;
         }
+        // ad.t:840-856; a function that appears in its own derivative is reused (`id`), so
+        // the emitter evaluates it once
+        case Op::Tan:   // a' (1 + tan^2)
+            r = bin(Op::Mul, diff(n.a, var), bin(Op::Add, cnst(1.0), bin(Op::Mul, id, id)));
+            break;
+        case Op::Tanh:   // a' (1 - tanh^2)
+            r = bin(Op::Mul, diff(n.a, var), bin(Op::Sub, cnst(1.0), bin(Op::Mul, id, id)));
+            break;
+        case Op::Sinh: r = bin(Op::Mul, diff(n.a, var), un(Op::Cosh, n.a)); break;
+        case Op::Cosh: r = bin(Op::Mul, diff(n.a, var), un(Op::Sinh, n.a)); break;
+        case Op::Asin:   // a' / sqrt(1 - a^2)
+            r = bin(Op::Div, diff(n.a, var), un(Op::Sqrt, bin(Op::Sub, cnst(1.0), bin(Op::Mul, n.a, n.a))));
+            break;
+        case Op::Acos:
+            r = un(Op::Neg, bin(Op::Div, diff(n.a, var), un(Op::Sqrt, bin(Op::Sub, cnst(1.0), bin(Op::Mul, n.a, n.a)))));
+            break;
+        case Op::Atan:   // a' / (1 + a^2)
+            r = bin(Op::Div, diff(n.a, var), bin(Op::Add, cnst(1.0), bin(Op::Mul, n.a, n.a)));
+            break;
+        case Op::Asinh:   // a' / sqrt(a^2 + 1)
+            r = bin(Op::Div, diff(n.a, var), un(Op::Sqrt, bin(Op::Add, bin(Op::Mul, n.a, n.a), cnst(1.0))));
+            break;
+        case Op::Acosh:   // a' / sqrt(a^2 - 1)
+            r = bin(Op::Div, diff(n.a, var), un(Op::Sqrt, bin(Op::Sub, bin(Op::Mul, n.a, n.a), cnst(1.0))));
+            break;
+        case Op::Log10:   // a' / (a ln 10)
+            r = bin(Op::Div, diff(n.a, var), bin(Op::Mul, n.a, cnst(std::log(10.0))));
+            break;
+        case Op::Atan2: {   // (a' b - b' a) / (a^2 + b^2); ad.t:845 has the sign of the second partial wrong
+            const int da = diff(n.a, var), db = diff(n.b, var);
+            r = bin(Op::Div, bin(Op::Sub, bin(Op::Mul, da, n.b), bin(Op::Mul, db, n.a)),
+                    bin(Op::Add, bin(Op::Mul, n.a, n.a), bin(Op::Mul, n.b, n.b)));
+            break;
+        }
         case Op::Select: r = select(n.a, diff(n.b, var), diff(n.d, var)); break;
         case Op::Sample: {   // op:getpartials (o.t:3274-3278): the derivative images, sampled
             const int da = diff(n.a, var), db = diff(n.b, var);
@@ -313,8 +358,10 @@ std::string Pool::str(int id) const {
         default: {
             static const char* names[] = {"", "", "", "", "", "+", "-", "*", "/", "neg", "sqrt", "sin", "cos",
                                           "exp", "log", "abs", "pow", "", "<", "<=", ">", ">=", "==", "!=", "&&",
-                                          "||", "!"};
-            if (n.b < 0) o << names[(int)n.op] << "(" << str(n.a) << ")";
+                                          "||", "!", "", "tan", "tanh", "sinh", "cosh", "asin", "acos", "atan",
+                                          "asinh", "acosh", "log10", "atan2"};
+            if (n.op == Op::Atan2) o << "atan2(" << str(n.a) << ", " << str(n.b) << ")";
+            else if (n.b < 0) o << names[(int)n.op] << "(" << str(n.a) << ")";
             else o << "(" << str(n.a) << " " << names[(int)n.op] << " " << str(n.b) << ")";
         }
     }

@@ -30,7 +30,16 @@ enum class Op : uint8_t {
     Lt, Le, Gt, Ge, Eq, Ne, And, Or, Not,
     Sample,   // bilinear sample of image i, channel ch, at (a, b); off2[0] / off2[1] = the
               // images sampled for d/dx and d/dy (-1: none) (ad.sampledimage, o.t:3266-3280)
+    // the rest of ad.t's elementary functions (ad.t:840-856); appended: an op's integer value
+    // names the cache images, so the ops above keep theirs
+    Tan, Tanh, Sinh, Cosh, Asin, Acos, Atan, Asinh, Acosh, Log10,
+    Atan2,    // the C library's atan2(a, b): the angle of the point (x = b, y = a)
 };
+
+// op(a) / op(a, b) of constants, in double (constant folding; the value a cached
+// transcendental takes where its argument reads outside the image, f(0))
+double fold1(Op op, double a);
+double fold2(Op op, double a, double b);
 
 struct Node {
     Op op = Op::Const;

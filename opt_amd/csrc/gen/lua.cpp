@@ -1211,6 +1211,10 @@ void Interp::install() {
         };
         m1("sqrt", std::sqrt); m1("sin", std::sin); m1("cos", std::cos); m1("exp", std::exp);
         m1("log", std::log); m1("abs", std::fabs); m1("floor", std::floor); m1("ceil", std::ceil);
+        m1("tan", std::tan); m1("tanh", std::tanh); m1("sinh", std::sinh); m1("cosh", std::cosh);
+        m1("asin", std::asin); m1("acos", std::acos); m1("atan", std::atan); m1("asinh", std::asinh);
+        m1("acosh", std::acosh); m1("log10", std::log10);
+        mt.t->h["atan2"] = builtin([](VList& a) { return VList{num(std::atan2(a.at(0).n, a.at(1).n))}; });
         mt.t->h["pi"] = num(M_PI);
         mt.t->h["huge"] = num(HUGE_VAL);
         mt.t->h["max"] = builtin([](VList& a) { double r = a.at(0).n; for (auto& v : a) r = std::max(r, v.n); return VList{num(r)}; });
@@ -1380,6 +1384,10 @@ void Interp::install() {
     f1("Sqrt", Op::Sqrt); f1("sqrt", Op::Sqrt); f1("sin", Op::Sin); f1("cos", Op::Cos); f1("exp", Op::Exp);
     f1("log", Op::Log); f1("abs", Op::Abs);
     def("pow", [this](VList& a) { return VList{zip(Op::Pow, a.at(0), a.at(1))}; });
+    // the rest of ad.t:840-856; atan2 is the C library's atan2(y, x)
+    f1("tan", Op::Tan); f1("tanh", Op::Tanh); f1("sinh", Op::Sinh); f1("cosh", Op::Cosh); f1("asin", Op::Asin);
+    f1("acos", Op::Acos); f1("atan", Op::Atan); f1("asinh", Op::Asinh); f1("acosh", Op::Acosh); f1("log10", Op::Log10);
+    def("atan2", [this](VList& a) { return VList{zip(Op::Atan2, a.at(0), a.at(1))}; });
     def("Dot3", [this](VList& a) {
         int s = P().bin(Op::Add, P().bin(Op::Add, P().bin(Op::Mul, comp(a.at(0), 0), comp(a.at(1), 0)),
                                           P().bin(Op::Mul, comp(a[0], 1), comp(a[1], 1))),
@@ -1440,7 +1448,8 @@ void Interp::install() {
         for (const char* n : {"Dim", "Param", "Unknown", "Array", "Image", "Graph", "InBounds"}) opt.t->h[n] = *globals_->vars[n];
         globals_->vars["opt"] = std::make_shared<Value>(opt);
         Value ad = table();
-        for (const char* n : {"sqrt", "sin", "cos", "exp", "log", "abs", "pow", "select"}) {
+        for (const char* n : {"sqrt", "sin", "cos", "exp", "log", "abs", "pow", "select", "tan", "tanh", "sinh", "cosh",
+                              "asin", "acos", "atan", "asinh", "acosh", "log10", "atan2"}) {
             auto it = globals_->vars.find(std::string(n) == "select" ? "Select" : n);
             if (it != globals_->vars.end()) ad.t->h[n] = *it->second;
         }

@@ -226,3 +226,70 @@ def read_ele(path):
     n = int(tok[0])
     a = np.array([int(x) for x in tok[3:3 + 5 * n]], np.int64).reshape(n, 5)
     return a[:, 1:].astype(np.int32)
+
+
+# ------------------------------------------------------------ 2-D pose graphs
+def read_g2o(path):
+    """The 2-D subset of the g2o text format: `VERTEX_SE2 id x y theta`, `EDGE_SE2 i j dx dy
+    dtheta I11 I12 I13 I22 I23 I33` (the upper triangle of the information matrix) and
+    `FIX id ...`; `#` starts a comment. Ids are renumbered 0 .. N-1 in the order their
+    VERTEX_SE2 lines appear. Returns (vertices (N, 3) float64, (ij (E, 2) int32, z (E, 3)
+    float64, info (E, 3, 3) float64), fixed int32 indices); with no FIX line the first
+    vertex is the anchor. An information matrix that is not positive definite is a
+    ValueError naming the edge."""
+    index, verts, raw_edges, fix_ids = {}, [], [], []
+    for ln, line in enumerate(open(path), 1):
+        t = line.split("#")[0].split()
+        if not t:
+            continue
+        if t[0] == "VERTEX_SE2":
+            if len(t) != 5:
+                raise ValueError("%s:%d: VERTEX_SE2 id x y theta" % (path, ln))
+            if int(t[1]) in index:
+                raise ValueError("%s:%d: vertex %s appears twice" % (path, ln, t[1]))
+            index[int(t[1])] = len(verts)
+            verts.append([float(x) for x in t[2:5]])
+        elif t[0] == "EDGE_SE2":
+            if len(t) != 12:
+                raise ValueError("%s:%d: EDGE_SE2 i j dx dy dtheta and 6 information entries" % (path, ln))
+            raw_edges.append((ln, int(t[1]), int(t[2]), [float(x) for x in t[3:12]]))
+        elif t[0] == "FIX":
+            fix_ids += [(ln, int(x)) for x in t[1:]]
+        else:
+            raise ValueError("%s:%d: unsupported record %s (VERTEX_SE2, EDGE_SE2 and FIX are read)" % (path, ln, t[0]))
+    E = len(raw_edges)
+    ij, z, info = np.zeros((E, 2), np.int32), np.zeros((E, 3)), np.zeros((E, 3, 3))
+    for k, (ln, a, b, v) in enumerate(raw_edges):
+        for q in (a, b):
+            if q not in index:
+                raise ValueError("%s:%d: edge %d -> %d names vertex %d, which has no VERTEX_SE2 line" % (path, ln, a, b, q))
+        ij[k] = index[a], index[b]
+        z[k] = v[:3]
+        i11, i12, i13, i22, i23, i33 = v[3:]
+        info[k] = [[i11, i12, i13], [i12, i22, i23], [i13, i23, i33]]
+        try:
+            np.linalg.cholesky(info[k])
+        except np.linalg.LinAlgError:
+            raise ValueError("%s:%d: the information matrix of edge %d -> %d is not positive definite"
+                             % (path, ln, a, b)) from None
+    for ln, q in fix_ids:
+        if q not in index:
+            raise ValueError("%s:%d: FIX names vertex %d, which has no VERTEX_SE2 line" % (path, ln, q))
+    fixed = sorted({index[q] for _, q in fix_ids}) if fix_ids else ([0] if verts else [])
+    return np.array(verts, np.float64).reshape(-1, 3), (ij, z, info), np.array(fixed, np.int32)
+
+
+def write_g2o(path, vertices, edges, fixed=None, ids=None) -> None:
+    """The inverse of read_g2o; ids (default 0 .. N-1) are the ids written for the vertices.
+    Numbers are written with repr, so a float64 round trip is exact."""
+    V = np.asarray(vertices, np.float64).reshape(-1, 3)
+    ij, z, info = edges
+    ids = list(range(len(V))) if ids is None else [int(i) for i in ids]
+    with open(path, "w") as f:
+        for i, v in zip(ids, V):
+            f.write("VERTEX_SE2 %d %r %r %r\n" % (i, float(v[0]), float(v[1]), float(v[2])))
+        if fixed is not None and len(fixed):
+            f.write("FIX " + " ".join(str(ids[int(k)]) for k in fixed) + "\n")
+        for (a, b), m, I in zip(np.asarray(ij, np.int64), np.asarray(z, np.float64), np.asarray(info, np.float64)):
+            vals = [m[0], m[1], m[2], I[0, 0], I[0, 1], I[0, 2], I[1, 1], I[1, 2], I[2, 2]]
+            f.write("EDGE_SE2 %d %d %s\n" % (ids[a], ids[b], " ".join(repr(float(x)) for x in vals)))

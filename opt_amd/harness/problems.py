@@ -682,3 +682,54 @@ def robust_nonrigid_alignment(src_v, src_f, tets, tgt_v, tgt_f, arg_order: str =
                 Offset=src_v.copy(), Angle=np.zeros((N, 3), np.float32), RobustWeights=np.ones(N, np.float32),
                 UrShape=src_v.copy(), Constraints=C, ConstraintNormals=CN, v0=v0, v1=v1,
                 average_edge_length=avg, spurious=np.array(spurious, np.int64))
+
+
+# -------------------------------------------------------------- pose_graph_2d
+def pose_graph_2d(vertices, edges, fixed, w_anchor: float = 1000.0):
+    """Arrays of energies/pose_graph_2d.t from a 2-D pose graph as formats.read_g2o returns
+    it: vertices (N, 3) of (x, y, theta); edges = (ij (E, 2), z (E, 3), info (E, 3, 3));
+    fixed = the indices of the anchored poses. Returns (arrays, dims): P = P0 the poses, A
+    the anchor flags, Z the measurements, U0 / U1 the rows of the upper Cholesky factor U of
+    each information matrix (info = U^T U, U = numpy.linalg.cholesky(info).T), the graph
+    slots i, j and the identity slot e; dims = [N, E].
+
+        v, e, fixed = formats.read_g2o("graph.g2o")
+        w, dims = problems.pose_graph_2d(v, e, fixed)
+        s = OptSolver(dims, "energies/pose_graph_2d.t", "LMGPU")
+        s.solve(problems.pose_graph_2d_params(w, lambda a: torch.from_numpy(a).cuda()))
+    """
+    V = np.asarray(vertices, np.float64).reshape(-1, 3)
+    ij, z, info = edges
+    ij = np.asarray(ij, np.int64).reshape(-1, 2)
+    z = np.asarray(z, np.float64).reshape(-1, 3)
+    info = np.asarray(info, np.float64).reshape(-1, 3, 3)
+    N, E = len(V), len(ij)
+    if E and (ij.min() < 0 or ij.max() >= N):
+        raise ValueError("pose_graph_2d: an edge names a pose outside 0..%d" % (N - 1))
+    try:
+        U = np.linalg.cholesky(info).transpose(0, 2, 1) if E else np.zeros((0, 3, 3))
+    except np.linalg.LinAlgError:
+        for k in range(E):   # which one
+            try:
+                np.linalg.cholesky(info[k])
+            except np.linalg.LinAlgError:
+                raise ValueError("pose_graph_2d: the information matrix of edge %d (%d -> %d) is not positive "
+                                 "definite" % (k, ij[k, 0], ij[k, 1])) from None
+        raise
+    A = np.zeros(N, np.float32)
+    A[np.asarray(fixed, np.int64)] = 1.0
+    P = V.astype(np.float32)
+    w = dict(N=N, E=E, w_anchor=float(w_anchor), P=P, P0=P.copy(), A=A, Z=z.astype(np.float32),
+             U0=np.ascontiguousarray(U[:, 0, :], np.float32),
+             U1=np.ascontiguousarray(np.stack([U[:, 1, 1], U[:, 1, 2], U[:, 2, 2]], 1).reshape(E, 3), np.float32),
+             i=ij[:, 0].astype(np.int32), j=ij[:, 1].astype(np.int32), e=np.arange(E, dtype=np.int32))
+    return w, [N, E]
+
+
+def pose_graph_2d_params(w: dict, conv=lambda a: a, double: bool = False) -> list:
+    """The parameter list of energies/pose_graph_2d.t in its declaration order; conv moves
+    each array where the solver's backend wants it (the unknown P in the plan's precision, a
+    copy: the solve writes it)."""
+    T = np.float64 if double else np.float32
+    return [w["w_anchor"], conv(np.array(w["P"], T, order="C"))] + \
+           [conv(np.ascontiguousarray(w[k])) for k in ("P0", "A", "Z", "U0", "U1", "i", "j", "e")]

@@ -1,0 +1,102 @@
+"""A synthetic grid-world 2-D pose graph at size on energies/pose_graph_2d.t (for information,
+no bar): S x S poses on a unit grid, a constraint from every pose to its right and to its
+upper neighbour (about 2 S^2), noisy measurements, random SPD information matrices, start
+poses off the truth with headings on different turns. fp32 Gauss-Newton steps with
+--iters PCG iterations: the wall time of one step and the plan's kernel table.
+
+The plan's table names the passes, not the kernels: `gen_apply` is one J^T J p (the prior's
+gen_apply and the constraints' gen_apply_graph together), `jtf` one J^T F with the
+preconditioner (gen_jtf and gen_jtf_graph together).
+
+  python tools/bench_pose_graph.py [--side 1000] [--iters 10] [--reps 5] [--out FILE]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from opt_amd import OptSolver  # noqa: E402
+from opt_amd.harness import problems  # noqa: E402
+
+
+def grid_world(S, seed=1):
+    rng = np.random.default_rng(seed)
+    yy, xx = np.mgrid[0:S, 0:S]
+    N = S * S
+    truth = np.stack([xx.reshape(-1), yy.reshape(-1), rng.uniform(-np.pi, np.pi, N)], 1).astype(np.float64)
+    idx = (xx + S * yy)
+    i = np.concatenate([idx[:, :-1].reshape(-1), idx[:-1, :].reshape(-1)])
+    j = np.concatenate([idx[:, 1:].reshape(-1), idx[1:, :].reshape(-1)])
+    order = rng.permutation(len(i))
+    i, j = i[order], j[order]
+    E = len(i)
+    c, s = np.cos(truth[i, 2]), np.sin(truth[i, 2])
+    dt = truth[j, :2] - truth[i, :2]
+    dth = truth[j, 2] - truth[i, 2]
+    z = np.stack([c * dt[:, 0] + s * dt[:, 1], -s * dt[:, 0] + c * dt[:, 1], np.arctan2(np.sin(dth), np.cos(dth))], 1)
+    z += rng.normal(0, 1, (E, 3)) * [0.02, 0.02, 0.01]
+    B = rng.normal(0, 1, (E, 3, 3))
+    info = 4.0 * (np.einsum("eab,ecb->eac", B, B) + 2.0 * np.eye(3))
+    V = truth + rng.normal(0, 1, (N, 3)) * [0.1, 0.1, 0.08]
+    V[:, 2] += 2 * np.pi * rng.integers(-1, 2, N)
+    return V, (np.stack([i, j], 1), z, info), [0]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--side", type=int, default=1000)
+    ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--out")
+    a = ap.parse_args()
+    V, edges, fixed = grid_world(a.side)
+    w, dims = problems.pose_graph_2d(V, edges, fixed, w_anchor=10.0)
+    del V, edges
+    cuda = lambda x: torch.from_numpy(x).cuda()  # noqa: E731
+    s = OptSolver(dims, os.path.join(ROOT, "energies", "pose_graph_2d.t"), "gaussNewtonGPU")
+    assert s.family() == "generic"
+    s.set_solver_params({"nIterations": 1, "lIterations": a.iters})
+
+    def one_step():
+        prm = problems.pose_graph_2d_params(w, cuda)
+        s.init(prm)
+        c0 = s.cost()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        s.step()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3, c0, s.cost()
+
+    one_step()   # warm-up: code object, incidence lists
+    runs = [one_step() for _ in range(a.reps)]
+    out = {"poses": dims[0], "constraints": dims[1], "pcg_iterations": a.iters, "precision": "fp32",
+           "solver": "gaussNewtonGPU", "device": torch.cuda.get_device_name(0),
+           "step_ms": sorted(r[0] for r in runs), "step_ms_median": float(np.median([r[0] for r in runs])),
+           "cost_before": runs[0][1], "cost_after_step": runs[0][2]}
+    # the kernel table, in a pass of its own (event pairs around every launch slow the step)
+    s.set_kernel_timing(1)
+    for _ in range(3):
+        one_step()
+    table = {}
+    for n in ("jtf", "gn_init", "gen_apply", "step2", "step3", "update", "cost", "precompute"):
+        cnt, ms = s.kernel_stat(n)
+        if cnt:
+            table[n] = {"launches": cnt, "us_per_launch": 1e3 * ms / cnt}
+    out["kernels"] = table
+    out["kernel_report"] = s.kernel_report().splitlines()
+    s.set_kernel_timing(0)
+    print(json.dumps({k: v for k, v in out.items() if k != "kernel_report"}))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        open(a.out, "w").write(json.dumps(out, indent=1) + "\n")
+
+
+if __name__ == "__main__":
+    main()
