@@ -58,8 +58,16 @@ $(RCCL_STUB): tests/rccl_stub/rccl_stub.cpp
 	$(HIPCC) -O2 -std=c++17 -fPIC -shared -Wl,-Bsymbolic -Wl,-soname,librccl_stub.so -o $@ $< -lrt
 rccl_stub: $(RCCL_STUB)
 
+# host-only dump of what the kernel generator emits (tools/gen_dump.cpp); not part of `all`
+GEN_DUMP ?= build/gen_dump
+GEN_DUMP_FLAGS ?= -O2
+$(GEN_DUMP): tools/gen_dump.cpp $(GEN_SRCS) $(HDRS) $(REDUCE_SRC)
+	@mkdir -p $(dir $@)
+	g++ -std=c++17 -Wall -Wno-unused-function $(GEN_DUMP_FLAGS) -I$(SRC_DIR) -I$(GEN_DIR) -o $@ tools/gen_dump.cpp $(GEN_SRCS)
+gen_dump: $(GEN_DUMP)
+
 clean:
 	rm -rf build $(LIB) $(RCCL_STUB)
 	$(MAKE) -C oracle clean
 
-.PHONY: all oracle clean rccl_stub
+.PHONY: all oracle clean rccl_stub gen_dump

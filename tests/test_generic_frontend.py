@@ -67,7 +67,7 @@ def test_generated_source_compiles(name):
 
 def test_strip_wave_index_form_per_kernel():
     """The strip kernels take the wave index through readfirstlane only when they read no
-    two-channel pair windows (codegen.cpp, OPT_AMD_GEN_WIDU=2, the default): image_warping's
+    two-channel pair windows (codegen_strip.cpp, OPT_AMD_GEN_WIDU=2, the default): image_warping's
     strips (Offset / UrShape pairs) ran 204-206 us with it against 165-166 without,
     shape_from_shading's 139-142 against 146-148."""
     if os.environ.get("OPT_AMD_GEN_WIDU") not in (None, "2"):
@@ -302,3 +302,30 @@ def test_sample_cache_falls_back_when_its_images_do_not_fit(tmp_path):
     lib, st, pr = _define(fits)
     assert pr
     lib.Opt_ProblemDelete(st, pr)
+
+
+def test_generate_is_reentrant():
+    """Plan creation is not serialised by the C ABI, so two host threads may generate at
+    once (ctypes releases the GIL): every concurrent result is the serial text. Energies:
+    transcendental and predicate caches with strips, the graph record cache,
+    ComputedArrays with tiles, a 1-D domain."""
+    import threading
+
+    names = ["image_warping", "arap_mesh_deformation", "shape_from_shading", "curve_smoothing"]
+    serial = {n: api.generic_source(E(n)) for n in names}
+    got = {n: [] for n in names}
+    start = threading.Barrier(len(names))
+
+    def work(n):
+        start.wait()
+        for _ in range(6):
+            got[n].append(api.generic_source(E(n)))
+
+    threads = [threading.Thread(target=work, args=(n,)) for n in names]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    for n in names:
+        assert len(got[n]) == 6
+        assert [g == serial[n] for g in got[n]] == [True] * 6, n
