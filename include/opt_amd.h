@@ -80,6 +80,29 @@ int OptAMD_PlanPreconditionerBlocks(Opt_Plan* plan, int maxImages, int* group, i
 int OptAMD_ApplyPreconditioner(Opt_State* state, Opt_Plan* plan, void** problemparams,
                                const void* r, void* z);
 
+/* Schur complement: Eliminate(X, ...) in an energy file names the unknown images of one
+ * index space (all of them, and another unknown-carrying space must remain), whose block C
+ * of A = J^T J (+ LM's diagonal) = [[B, E], [E^T, C]] is block-diagonal: one block per
+ * element, no residual reads two elements of the group (else Opt_ProblemDefine returns
+ * NULL and names the cause). The statement turns the block preconditioner on. PCG then runs
+ * on S delta_r = b_r - E M^-1 b_e, S = B - E M^-1 E^T, preconditioned with the retained
+ * groups' blocks, and delta_e = M^-1 (b_e - E^T delta_r) follows; M_e = C_e, or
+ * C_e + diag(CtC_e) on an LMGPU plan. An eliminated element whose Cholesky pivot is
+ * <= sqrt(eps) * max_i (M_e)_ii is held fixed for that step (M_e^-1 = 0), as excluded
+ * elements are. The unknown vector keeps its layout (OptAMD_PlanUnknownLayout).
+ *
+ * Writes, for each unknown image (layout order, up to maxImages), 1 if the plan eliminates
+ * it, else 0 (all 0 on a plan without the statement); returns the number of unknown images,
+ * -1 for a NULL plan. */
+int OptAMD_PlanEliminated(Opt_Plan* plan, int maxImages, int* eliminated);
+
+/* Sp = S p at the current unknowns (device vectors of OptAMD_PlanUnknownCount elements;
+ * on an LMGPU plan with CtC_r p and M at the plan's current trust-region radius). The
+ * eliminated entries of p are ignored, those of Sp are 0. Returns 0, or 1 on a plan without
+ * Eliminate. OptAMD_ApplyJTJ on such a plan is still the full J^T J p. */
+int OptAMD_ApplyReduced(Opt_State* state, Opt_Plan* plan, void** problemparams,
+                        const void* p, void* Sp);
+
 /* Ap = J^T J p at the current unknowns (+ CtC*p for LM plans, with the CtC of the
  * last LM step) and *p_dot_Ap = p.Ap (reference kernels.PCGStep1,
  * solverGPUGaussNewton.t:607-632, with fmap.applyJTJ o.t:2770-2830). Excluded

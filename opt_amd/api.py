@@ -64,6 +64,8 @@ _SIGNATURES = [
     ("OptAMD_PlanPreconditionerBlocks", ctypes.c_int, [_VP, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
                                                        ctypes.POINTER(ctypes.c_int)]),
     ("OptAMD_ApplyPreconditioner", ctypes.c_int, [_VP, _VP, ctypes.POINTER(_VP), _VP, _VP]),
+    ("OptAMD_PlanEliminated", ctypes.c_int, [_VP, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
+    ("OptAMD_ApplyReduced", ctypes.c_int, [_VP, _VP, ctypes.POINTER(_VP), _VP, _VP]),
     ("OptAMD_TimeApplyJTJ", ctypes.c_double, [_VP, _VP, ctypes.POINTER(_VP), _VP, _VP, ctypes.c_int]),
     ("OptAMD_SetKernelTiming", None, [_VP, ctypes.c_int]),
     ("OptAMD_KernelStat", ctypes.c_int, [_VP, ctypes.c_char_p, ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_double)]),
@@ -304,6 +306,23 @@ class OptSolver:
         if self.lib.OptAMD_ApplyPreconditioner(self.state, self.plan, pk.ptr, _ptr(r), _ptr(z)):
             self._raise_plan_error()
             raise OptError("OptAMD_ApplyPreconditioner failed")
+
+    def eliminated(self):
+        """0 / 1 per unknown image: whether the plan eliminates it (Eliminate in the energy
+        file; OptAMD_PlanEliminated). All 0 on a plan without the statement."""
+        f = (ctypes.c_int * 4)()
+        k = self.lib.OptAMD_PlanEliminated(self.plan, 4, f)
+        if k < 0:
+            raise OptError("OptAMD_PlanEliminated failed")
+        return list(f)[:k]
+
+    def apply_reduced(self, problem_params, p, Sp) -> None:
+        """Sp = S p, the Schur complement's product at the current unknowns
+        (OptAMD_ApplyReduced); raises on a plan without Eliminate."""
+        pk = ParamPack(problem_params)
+        if self.lib.OptAMD_ApplyReduced(self.state, self.plan, pk.ptr, _ptr(p), _ptr(Sp)):
+            self._raise_plan_error()
+            raise OptError("OptAMD_ApplyReduced failed (a plan without Eliminate has no reduced system)")
 
     def eval_cost(self, problem_params) -> float:
         pk = ParamPack(problem_params)

@@ -20,7 +20,8 @@
 //
 // generate() keeps all its state in one Ctx (codegen_ctx.h) and is re-entrant. The Body
 // expression emitter is in codegen_body.cpp, the register strips in codegen_strip.cpp, the
-// graph gathers and the block preconditioner's PCG kernels in codegen_graph.cpp.
+// graph gathers and the block preconditioner's PCG kernels in codegen_graph.cpp, the Schur
+// complement's kernels (Eliminate) in codegen_schur.cpp.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -52,8 +53,10 @@ static Knobs read_knobs() {
 Analysis::Analysis(const GModel& m)
     : nd(m.unknown_dims()), unk(m.unknown_images()), uslot(m.images.size(), -1), mspace(m.multi()),
       uspaces(mspace ? m.unknown_spaces() : std::vector<int>{0}), blockpre(m.block_preconditioner),
-      groups(blockpre ? m.block_groups() : std::vector<GBlockGroup>{}) {
+      groups(blockpre ? m.block_groups() : std::vector<GBlockGroup>{}), elim_group(-1) {
     for (size_t k = 0; k < unk.size(); ++k) uslot[unk[k]] = (int)k;
+    for (size_t g = 0; g < groups.size() && m.schur(); ++g)
+        if (groups[g].space == m.elim_space) elim_group = (int)g;
     for (size_t ri = 0; ri < m.residuals.size(); ++ri) {
         const GResidual& r = m.residuals[ri];
         if (r.graph >= 0) continue;
@@ -901,6 +904,7 @@ GenSource generate(GModel& m, bool dbl, bool off32) {
     emit_cost(cx, o);
     emit_graph_gathers(cx, o);
     emit_block_pcg(cx, o);
+    emit_schur(cx, o);
     char note[128];
     snprintf(note, sizeof(note), "// apply: %s (%.2f residual instances per centred residual)\n",
              gs.has_strip ? "gen_apply_strip" : gs.prefer_tiled ? "gen_apply_tiled" : "gen_apply",

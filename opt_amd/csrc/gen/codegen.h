@@ -63,6 +63,8 @@ struct GenSource {
     // gen_apply_graph adds the centred residuals' terms itself (1-D vertex domains): the
     // plan launches no gen_apply before it
     bool graph_apply_centred = false;
+    // gen_schur_rhs / gen_schur_elim / gen_schur_apply emitted (Eliminate, codegen_schur.cpp)
+    bool has_schur = false;
 };
 
 // Generate the kernels for `m` in float (dbl = false) or double. off32: every array a

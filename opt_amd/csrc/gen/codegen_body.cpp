@@ -282,7 +282,9 @@ std::string Body::read(const Node& n, const char* vname) {
     const GImage& im = M_.images[n.i];
     const std::string ch = std::to_string(im.channels), c = std::to_string(n.ch);
     std::string base, idx;
-    if (vname) {
+    if (vname && C_.vec_base) {
+        base = C_.vec_base(n.i, vname);
+    } else if (vname) {
         base = std::string(vname) + " + a.uoff[" + std::to_string(C_.uslot[n.i]) + "]";
     } else {
         base = img_ptr(n.i);

@@ -90,6 +90,9 @@ struct Analysis {
     // that element's diagonal block of J^T J: blk[base_g + j * N_g + e], entry j slowest.
     bool blockpre;
     std::vector<GBlockGroup> groups;
+    // Eliminate (GModel::eliminated): the eliminated group among `groups`, -1 without the
+    // statement; PCG runs on the Schur complement over the other groups (codegen_schur.cpp)
+    int elim_group;
 
     // the tiled / strip forms (2-D centred, one space; analyse_tiles)
     std::vector<int> cres;        // centred residual ids
@@ -133,6 +136,12 @@ struct Ctx : Analysis {
     std::string blk_base(int g) const;
     int blk_row(int g, int image, int ch) const;
     std::string blk_arg() const { return blockpre ? ", T* __restrict__ blk" : ""; }
+    // Schur kernels: the eliminated space, and where a read of the PCG vector `vname` at
+    // unknown image `image` starts (set by the Schur emitters while they emit: the eliminated
+    // images of "w" start inside the compact scratch vector; unset: vname + a.uoff[image])
+    bool schur() const { return elim_group >= 0; }
+    int elim_space() const { return groups[elim_group].space; }
+    std::function<std::string(int image, const char* vname)> vec_base;
 };
 inline int tri(int i, int j) { return i >= j ? i * (i + 1) / 2 + j : j * (j + 1) / 2 + i; }
 
@@ -214,6 +223,11 @@ void centred_cost_terms(Ctx& cx, Body& b, const std::vector<int>& res);
 void emit_cost(Ctx& cx, std::ostringstream& o);                      // gen_cost
 void emit_graph_gathers(Ctx& cx, std::ostringstream& o);             // gen_jtf_graph, gen_apply_graph
 void emit_block_pcg(const Ctx& cx, std::ostringstream& o);           // gen_blk_*
+// One vertex's gather over its incidence lists (codegen_graph.cpp): J^T F's terms, or with
+// `apply` J^T J p's. schur 1: p read at the retained images only (E^T p_r at a vertex of the
+// eliminated space); 2: eliminated images read from "w" instead of "p"
+void graph_gather(Ctx& cx, std::ostringstream& o, bool apply, int sp, int schur = 0);
+void emit_schur(Ctx& cx, std::ostringstream& o);                     // gen_schur_rhs, gen_schur_elim, gen_schur_apply
 
 }  // namespace gen
 }  // namespace optamd

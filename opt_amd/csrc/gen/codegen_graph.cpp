@@ -17,7 +17,9 @@ namespace gen {
 // Several index spaces: the vertices of space sp gather through the slots that index sp
 // (an unknown read at slot k lies over slot k's space, so only sp's unknowns accumulate);
 // the other slots' vertices come from the gnb copies as before.
-static void graph_gather(Ctx& cx, std::ostringstream& o, bool apply, int sp) {
+// schur (codegen_schur.cpp): 1 the sum J p takes the retained images only (u_e = (E^T p_r)_e
+// at a vertex of the eliminated space); 2 it reads the eliminated images from "w"
+void graph_gather(Ctx& cx, std::ostringstream& o, bool apply, int sp, int schur) {
     GModel& m = cx.m;
     Pool& P = cx.P;
     GenSource& gs = cx.gs;
@@ -56,10 +58,12 @@ static void graph_gather(Ctx& cx, std::ostringstream& o, bool apply, int sp) {
                 if (apply) {
                     std::string sum = "(T)0";
                     for (int u : r.unknowns) {
+                        const bool elim = schur && m.is_eliminated(P.at(u).i);
+                        if (schur == 1 && elim) continue;
                         const int gu = P.diff(r.expr, u);
                         double gv;
                         if (P.is_const(gu, &gv) && gv == 0.0) continue;
-                        sum += " + " + b.v(gu) + " * " + b.vec(u, "p");
+                        sum += " + " + b.v(gu) + " * " + b.vec(u, schur == 2 && elim ? "w" : "p");
                     }
                     R = "jp" + std::to_string(idx++);
                     b.line("const T " + R + " = " + sum + ";");
@@ -372,17 +376,35 @@ void emit_block_pcg(const Ctx& cx, std::ostringstream& o) {
          "        for (int i = 0; i < C; ++i) zout[x[i]] = zv[i];\n"
          "    }\n"
          "}\n"
+      << (cx.schur() ?
+         "template <class G> __device__ __forceinline__ void opt_blk_clear_group(const GenArgs& a, T* z, T* p) {\n"
+         "    constexpr int C = G::C;\n"
+         "    const long long bN = G::n(a);\n"
+         "    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < bN; e += (long long)gridDim.x * 256) {\n"
+         "        long long x[C];\n"
+         "        G::ix(a, e, x);\n"
+         "#pragma unroll\n"
+         "        for (int i = 0; i < C; ++i) { z[x[i]] = (T)0; p[x[i]] = (T)0; }\n"
+         "    }\n"
+         "}\n" : "") <<
          // LM inner-loop exit test on the launch's total q (stencil_driver.h zeta_test)
          "__device__ __forceinline__ void opt_blk_zeta(double q1, double* q0, int* zstop, int liter, float q_tol) {\n"
+      // Eliminate: the loop's q is the reduced system's; q0[1] holds this step's constant
+      // 1/2 b_e.M^-1 b_e (gen_schur_rhs), their sum the full model's value at (delta_r, delta_e*(delta_r))
+      << (cx.schur() ? "    q1 += q0[1];\n" : "") <<
          "    const T Q1 = (T)q1, Q0 = (T)*q0;\n"
          "    const T zeta = (T)(liter + 1) * (Q1 - Q0) / Q1;\n"
          "    if (zeta < (T)q_tol) *zstop = 1;\n"
          "    else *q0 = (double)Q1;\n"
          "}\n";
-    auto each = [&](const std::string& call) {
+    // Eliminate: during the PCG loop the eliminated group's r, z, p, Ap and delta are exactly
+    // zero, so its elements take `elim` instead ("": nothing to do): gen_blk_init only clears
+    // z and p (gen_schur_rhs has inverted the group's blocks already), the steps skip it
+    auto each = [&](const std::string& call, const std::string& elim = "") {
         std::string s;
         for (size_t g = 0; g < groups.size(); ++g) {
-            std::string c = call;
+            std::string c = (int)g == cx.elim_group ? elim : call;
+            if (c.empty()) continue;
             c.replace(c.find("GROUP"), 5, "OptGroup" + std::to_string(g));
             s += "    " + c + "\n";
         }
@@ -391,7 +413,7 @@ void emit_block_pcg(const Ctx& cx, std::ostringstream& o) {
     o << "extern \"C\" __global__ __launch_bounds__(256) void gen_blk_init(GenArgs a, const T* __restrict__ r, const T* __restrict__ pre,\n"
          "        const T* __restrict__ ctc, T* __restrict__ blk, T* __restrict__ z, T* __restrict__ p, int lm, ReduceSlot rs) {\n"
          "    T acc = 0;\n"
-      << each("acc += opt_blk_init_group<GROUP>(a, r, pre, ctc, blk, z, p, lm);")
+      << each("acc += opt_blk_init_group<GROUP>(a, r, pre, ctc, blk, z, p, lm);", "opt_blk_clear_group<GROUP>(a, z, p);")
       << "    double v[1] = {(double)acc};\n    block_reduce_publish<1>(v, rs, blockIdx.x);\n}\n";
     o << "extern \"C\" __global__ __launch_bounds__(256) void gen_blk_step2(GenArgs a, const T* __restrict__ p, const T* __restrict__ Ap,\n"
          "        const T* __restrict__ blk, const T* __restrict__ b, T* __restrict__ r, T* __restrict__ delta, T* __restrict__ z,\n"
@@ -419,7 +441,7 @@ void emit_block_pcg(const Ctx& cx, std::ostringstream& o) {
          "    double tot[2];\n"
          "    if (block_reduce_publish<2>(v, rs, blockIdx.x, tot) && zon) opt_blk_zeta(tot[1], q0, zstop, liter, q_tol);\n}\n";
     o << "extern \"C\" __global__ __launch_bounds__(256) void gen_blk_apply(GenArgs a, const T* __restrict__ blk, const T* __restrict__ rin, T* __restrict__ zout) {\n"
-      << each("opt_blk_apply_group<GROUP>(a, blk, rin, zout);") << "}\n";
+      << each("opt_blk_apply_group<GROUP>(a, blk, rin, zout);", "opt_blk_apply_group<GROUP>(a, blk, rin, zout);") << "}\n";
 }
 
 }  // namespace gen

@@ -8,7 +8,7 @@
 // comparisons, arithmetic, string concatenation, and the few library functions energy
 // files use (print, pairs, ipairs, tostring, type, unpack, math.*).
 // DSL: Dim, Param, Unknown, Array / Image, Graph (+ G.slot), UsePreconditioner, Exclude,
-// Energy, Select, InBounds, InBoundsExpanded, Index, Stencil, eq / greater / greatereq /
+// Eliminate, Energy, Select, InBounds, InBoundsExpanded, Index, Stencil, eq / greater / greatereq /
 // less / lesseq / notEq, And / Or / Not / All, Dot3, Sqrt, normalize, length, Vector,
 // Rotate2D, Rotate3D, Matrix3x3Mul, sin / cos / exp / log / abs / pow; image access
 // X(dx, dy[, ch]), X(G.v) and component access e(i), e:dot(f).
@@ -578,6 +578,7 @@ public:
     }
     void run(const Block& b) { exec_block(b, std::make_shared<Scope>(Scope{{}, globals_})); }
     void finish();
+    void check_eliminate();
 
 private:
     GModel* m_;
@@ -983,6 +984,7 @@ private:
         return v.id;
     }
     int lp_counter_ = 0;
+    int n_eliminate_ = 0;   // Eliminate statements seen
     void note_index(int idx) { m_->n_params_total = std::max(m_->n_params_total, idx + 1); }
     int channels_of(const Value& t) {
         if (t.k == V::Type) return t.id;
@@ -1265,6 +1267,16 @@ void Interp::install() {
         m_->use_preconditioner = !a.empty() && truthy(a[0]);
         // "block": the block-Jacobi form (any other non-nil argument is the reference's true)
         m_->block_preconditioner = !a.empty() && a[0].k == V::Str && a[0].s == "block";
+        return VList{};
+    });
+    def("Eliminate", [this](VList& a) {
+        if (++n_eliminate_ > 1) err("a second Eliminate (one group of unknowns can be eliminated)");
+        if (a.empty()) err("Eliminate(X, ...) names unknown images");
+        for (size_t i = 0; i < a.size(); ++i) {
+            if (a[i].k != V::Image || !m_->images[a[i].id].unknown)
+                err("Eliminate: argument " + std::to_string(i + 1) + " is not an unknown image");
+            if (!m_->is_eliminated(a[i].id)) m_->eliminated.push_back(a[i].id);
+        }
         return VList{};
     });
     def("Exclude", [this](VList& a) {
@@ -1674,6 +1686,57 @@ void Interp::finish() {
         r.unknowns.assign(unk.begin(), unk.end());
         m_->residuals.push_back(r);
     }
+    check_eliminate();
+}
+
+// Eliminate(X, ...): the group must be all unknown images of one index space, leave another
+// unknown-carrying space, and be decoupled: every residual reads at most one element of the
+// group's space, so that the group's block of J^T J is block-diagonal (one C x C block per
+// element) and the Schur complement on the other spaces needs only per-element inverses.
+void Interp::check_eliminate() {
+    if (m_->eliminated.empty()) return;
+    const std::vector<int> unk = m_->unknown_images();
+    const int sp = m_->images[m_->eliminated[0]].space;
+    for (int k : m_->eliminated)
+        if (m_->images[k].space != sp)
+            throw LuaError("Eliminate: " + m_->images[m_->eliminated[0]].name + " over " + space_name(sp) + " and " +
+                           m_->images[k].name + " over " + space_name(m_->images[k].space) +
+                           " lie over different index spaces (a group is the unknowns of one space)");
+    for (int k : unk)
+        if (m_->images[k].space == sp && !m_->is_eliminated(k))
+            throw LuaError("Eliminate: unknown " + m_->images[k].name + " over " + space_name(sp) +
+                           " is not named (a group is all unknown images of its index space)");
+    if (m_->unknown_spaces().size() < 2)
+        throw LuaError("Eliminate: no unknown-carrying index space would remain beside " + space_name(sp));
+    std::sort(m_->eliminated.begin(), m_->eliminated.end(),
+              [&](int a, int b) { return m_->images[a].index < m_->images[b].index; });
+    auto offset = [](const Node& n) { return n.off[0] != 0 || n.off[1] != 0 || n.off[2] != 0; };
+    for (auto& c : m_->computed)
+        for (auto& g : c.grads) {
+            if (g.u < 0) continue;
+            const Node n = P().at(g.u);
+            if (m_->is_eliminated(n.i) && offset(n))
+                throw LuaError("Eliminate: not decoupled: ComputedArray '" + m_->images[c.image].name + "' depends on " +
+                               m_->images[n.i].name + " at an offset");
+        }
+    for (auto& r : m_->residuals) {
+        int slot = -1;
+        for (int u : r.unknowns) {
+            const Node n = P().at(u);
+            if (!m_->is_eliminated(n.i)) continue;
+            if (r.graph < 0 && offset(n))
+                throw LuaError("Eliminate: not decoupled: a centred residual over " + space_name(sp) + " reads " +
+                               m_->images[n.i].name + " at a non-zero offset");
+            if (r.graph >= 0 && slot >= 0 && n.slot != slot)
+                throw LuaError("Eliminate: not decoupled: a residual of graph '" + m_->graphs[r.graph].name + "' reads " +
+                               space_name(sp) + " through two slots ('" +
+                               m_->graphs[r.graph].slot_names[std::min(slot, n.slot)] + "', '" +
+                               m_->graphs[r.graph].slot_names[std::max(slot, n.slot)] + "')");
+            if (r.graph >= 0) slot = n.slot;
+        }
+    }
+    m_->elim_space = sp;
+    m_->use_preconditioner = m_->block_preconditioner = true;   // as UsePreconditioner("block")
 }
 
 }  // namespace

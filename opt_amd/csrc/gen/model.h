@@ -86,7 +86,18 @@ struct GModel {
     // UsePreconditioner("block"): PCG preconditioned with the inverse of each element's
     // diagonal block of J^T J over all unknown channels of its index space
     bool block_preconditioner = false;
-    std::string unsupported;       // first construct the generic path cannot lower
+    // Eliminate(X, ...): the unknown images of one index space whose diagonal blocks of J^T J
+    // decouple (no residual reads two of its elements); PCG then runs on the Schur complement
+    // over the other spaces (build_model checks the group, turns the block preconditioner on)
+    std::vector<int> eliminated;   // image ids, unknown_images() order
+    int elim_space = -1;           // their space, -1 = no Eliminate
+    bool schur() const { return elim_space >= 0; }
+    bool is_eliminated(int image) const {
+        for (int k : eliminated)
+            if (k == image) return true;
+        return false;
+    }
+    std::string unsupported;      // first construct the generic path cannot lower
     int n_params_total = 0;
 
     int unknown_dims() const;      // dimensionality of the (first) unknowns' index space

@@ -147,6 +147,8 @@ bool generic_accepts(const std::string& text, ProblemSpec* spec, std::string* er
     spec->text = text;
     spec->use_preconditioner = m.use_preconditioner;
     spec->block_preconditioner = m.block_preconditioner;
+    spec->eliminate.clear();
+    for (int k : m.eliminated) spec->eliminate.push_back(m.images[k].name);
     spec->family = "generic";
     return true;
 }
@@ -195,6 +197,8 @@ bool generic_signature(const std::string& text, std::string* sig, bool* use_pre,
              std::to_string(r.unknowns.size()) + ":" + m.pool.str(r.expr) + ";";
     // (only when requested: every other energy's signature is what it always was)
     if (m.block_preconditioner) s += "B;";
+    // Eliminate: the group's index space (such a file always runs on generated kernels)
+    if (m.schur()) s += "S" + std::to_string(m.elim_space) + ";";
     *sig = s;
     if (use_pre) *use_pre = m.use_preconditioner;
     return true;
@@ -510,6 +514,42 @@ public:
                                  &zt.on});
     }
     void block_apply(const T* rin, T* zout, hipStream_t s) { launch(k_blk_apply_, s, {&a_, &blk_, &rin, &zout}); }
+
+    // ---- Schur complement (Eliminate(X, ...); StencilPlan: HasSchur; gen/codegen_schur.cpp) ----
+    // The plan owns two compact vectors of schur_entries() values (the eliminated images'
+    // elements): w (M^-1-sized products) and the stash of b_e. schur_rhs inverts the eliminated
+    // blocks in place (before block_init, which then skips them), stashes and clears b_e, leaves
+    // w = M^-1 b_e and publishes 1/2 b_e.M^-1 b_e; schur_elim is w = -M^-1 E^T p, or with the
+    // stash the back-substitution into the full vector `out`; schur_apply is Ap = B p + E w.
+    bool schur() const { return m_.schur(); }
+    long long schur_entries() const {
+        long long n = 0;
+        for (int k : m_.eliminated) n += pixels_of(k) * m_.images[k].channels;
+        return n;
+    }
+    void set_schur_buffers(T* w, T* be) { w_ = w; be_ = be; }
+    // per unknown image (VecLayout order): 1 if eliminated
+    int eliminated(int max_images, int* flag) const {
+        for (size_t k = 0; k < unk_.size() && (int)k < max_images; ++k)
+            if (flag) flag[k] = m_.is_eliminated(unk_[k]) ? 1 : 0;
+        return (int)unk_.size();
+    }
+    void schur_rhs(const T* ctc, T* r, T* b, int lm, ReduceSlot rs, hipStream_t s) {
+        launch(k_schur_rhs_, s, {&a_, &blk_, &ctc, &r, &b, &be_, &w_, &lm, &rs});
+    }
+    void schur_elim(const T* p, hipStream_t s) {
+        const T* rhs = nullptr;
+        int full = 0;
+        launch(k_schur_elim_, s, {&a_, &blk_, &p, &rhs, &w_, &full});
+    }
+    void schur_back(T* delta, hipStream_t s) {
+        const T* p = delta;
+        int full = 1;
+        launch(k_schur_elim_, s, {&a_, &blk_, &p, &be_, &delta, &full});
+    }
+    void schur_apply(const T* p, T* Ap, const T* dadd, const int* stop, ReduceSlot rs, hipStream_t s) {
+        launch(k_schur_apply_, s, {&a_, &p, &w_, &Ap, &dadd, &stop, &rs});
+    }
     void apply(const T* p, T* Ap, const T* dadd, const int* stop, ReduceSlot rs, hipStream_t s) {
         if (!src_.has_graph) {
             int finish = 1;
@@ -648,6 +688,11 @@ private:
         if (m_.block_preconditioner) {
             for (auto kv : {std::make_pair(&k_blk_init_, "gen_blk_init"), std::make_pair(&k_blk_step2_, "gen_blk_step2"),
                             std::make_pair(&k_blk_half2_, "gen_blk_half2"), std::make_pair(&k_blk_apply_, "gen_blk_apply")})
+                OPT_HIP_CHECK(hipModuleGetFunction(kv.first, mod_, kv.second));
+        }
+        if (src_.has_schur) {
+            for (auto kv : {std::make_pair(&k_schur_rhs_, "gen_schur_rhs"), std::make_pair(&k_schur_elim_, "gen_schur_elim"),
+                            std::make_pair(&k_schur_apply_, "gen_schur_apply")})
                 OPT_HIP_CHECK(hipModuleGetFunction(kv.first, mod_, kv.second));
         }
         // (the strip J^T F has no block accumulation: block energies keep the gather)
@@ -795,6 +840,8 @@ private:
     hipFunction_t k_blk_init_{}, k_blk_step2_{}, k_blk_half2_{}, k_blk_apply_{};
     std::vector<gen::GBlockGroup> groups_;   // block preconditioner: empty without it
     T* blk_ = nullptr;                       // the plan's block buffer (set_block_buffer)
+    hipFunction_t k_schur_rhs_{}, k_schur_elim_{}, k_schur_apply_{};
+    T *w_ = nullptr, *be_ = nullptr;         // the plan's compact Schur vectors (set_schur_buffers)
 };
 
 std::unique_ptr<Plan> make_generic_plan(const ProblemSpec& spec, const StateOptions& opts, const unsigned* dims,
@@ -819,6 +866,11 @@ std::unique_ptr<Plan> make_generic_plan(const ProblemSpec& spec, const StateOpti
             return nullptr;
         }
     long long nflags = 0;
+    if (m.schur() && (opts.materialized || opts.fused_jtj)) {
+        *err = "generic: no materialized Jacobian (useMaterializedJTJ / useFusedJTJ) with Eliminate: the Schur "
+               "complement runs matrix-free";
+        return nullptr;
+    }
     if (m.multi()) {
         if (opts.materialized || opts.fused_jtj) {
             *err = "generic: no materialized Jacobian (useMaterializedJTJ / useFusedJTJ) for an energy over several index spaces";

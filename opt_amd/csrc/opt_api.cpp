@@ -250,6 +250,14 @@ int OptAMD_ApplyPreconditioner(Opt_State* state, Opt_Plan* plan, void** params, 
         return 1;
     return guarded(plan, "OptAMD_ApplyPreconditioner", 1, [&] { return plan->impl->apply_preconditioner(params, r, z); });
 }
+int OptAMD_PlanEliminated(Opt_Plan* plan, int maxImages, int* eliminated) {
+    if (!valid_plan(plan, "OptAMD_PlanEliminated")) return -1;
+    return plan->impl->eliminated(maxImages, eliminated);
+}
+int OptAMD_ApplyReduced(Opt_State* state, Opt_Plan* plan, void** params, const void* p, void* Sp) {
+    if (!valid_state(state, "OptAMD_ApplyReduced") || !valid_plan(plan, "OptAMD_ApplyReduced") || !p || !Sp) return 1;
+    return guarded(plan, "OptAMD_ApplyReduced", 1, [&] { return plan->impl->apply_reduced(params, p, Sp); });
+}
 int OptAMD_ApplyJTJ(Opt_State* state, Opt_Plan* plan, void** params, const void* p, void* Ap,
                     double* pAp) {
     if (!valid_state(state, "OptAMD_ApplyJTJ") || !valid_plan(plan, "OptAMD_ApplyJTJ") || !p || !Ap)

@@ -154,6 +154,21 @@ public:
         return 1;
     }
 
+    // Eliminate (include/opt_amd.h): per unknown image 1 if the plan eliminates it (all 0 on
+    // other plans); the number of unknown images.
+    virtual int eliminated(int max_images, int* flag) const {
+        const int n = unknown_layout(0, nullptr, nullptr, nullptr);
+        for (int k = 0; k < n && k < max_images; ++k)
+            if (flag) flag[k] = 0;
+        return n;
+    }
+    // Sp = S p, the Schur complement's product at the current unknowns (device vectors of
+    // unknown_count() elements); 1 where the plan eliminates nothing.
+    virtual int apply_reduced(void** params, const void* p, void* Sp) {
+        (void)params; (void)p; (void)Sp;
+        return 1;
+    }
+
     void set_solver_param(const char* name, const void* value);
     // the device scalar slots (red_.scalars) to the host, up to n; the count copied
     int scalars(double* out, int n);

@@ -265,6 +265,13 @@ struct Parser {
                     spec->use_preconditioner = true;
                     spec->block_preconditioner = (t[a[0].first].text == "block");
                 }
+            } else if (f == "Eliminate") {
+                // the group by the variables' names; the general front end resolves and checks
+                // it (gen/lua.cpp check_eliminate) and turns the block preconditioner on
+                args(i + 1, &a);
+                for (auto& x : a)
+                    if (is_single(x, Tk::Name)) spec->eliminate.push_back(t[x.first].text);
+                spec->use_preconditioner = spec->block_preconditioner = true;
             } else if (f == "Exclude") {
                 spec->n_exclude++;
             } else if (f == "ComputedArray") {

@@ -41,6 +41,7 @@ struct ProblemSpec {
     std::vector<DeclGraph> graphs;
     bool use_preconditioner = false;  // default: opt.ProblemSpec, API/src/o.t:258
     bool block_preconditioner = false;   // UsePreconditioner("block"): generated kernels only
+    std::vector<std::string> eliminate;  // Eliminate(X, ...): the group's unknowns (generated kernels only)
     int n_exclude = 0;
     std::vector<std::string> computed_arrays;
     bool uses_sampled_image = false;

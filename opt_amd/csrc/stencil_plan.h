@@ -184,6 +184,30 @@ struct HasBlockPre : std::false_type {};
 template <class Op>
 struct HasBlockPre<Op, std::void_t<decltype(std::declval<const Op&>().block_pre())>> : std::true_type {};
 
+// Ops that can eliminate one group of unknowns (GenericOp for Eliminate(X, ...)): schur()
+// says whether this energy asked for it (then block_pre() holds too). PCG then runs on the
+// Schur complement S = B - E M^-1 E^T over the retained unknowns, in the full vector layout
+// with the eliminated entries of p, r, z, Ap and delta exactly zero: pcg_loop's block path as
+// it is, with the apply replaced by schur_elim (w = -M^-1 E^T p) + schur_apply (B p + E w);
+// before the loop schur_rhs (M_e^-1, the stash of b_e, w = M^-1 b_e) and one schur_apply of
+// p = 0 give the reduced right-hand side b_r - E M^-1 b_e; after it schur_back writes
+// delta_e = M^-1 (b_e - E^T delta_r), and the update, model cost and cost see the full delta.
+template <class Op, class = void>
+struct HasSchur : std::false_type {};
+template <class Op>
+struct HasSchur<Op, std::void_t<decltype(std::declval<const Op&>().schur())>> : std::true_type {};
+
+// r -= Ap (and b = r, LM): the reduced right-hand side from Ap = E M^-1 b_e
+template <typename T>
+__global__ __launch_bounds__(kBlock) void schur_sub_kernel(long long n, T* __restrict__ r, const T* __restrict__ Ap,
+                                                           T* __restrict__ b) {
+    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x) {
+        const T v = r[e] - Ap[e];
+        r[e] = v;
+        if (b) b[e] = v;
+    }
+}
+
 // z = pre r (OptAMD_ApplyPreconditioner on a scalar plan)
 template <typename T>
 __global__ __launch_bounds__(kBlock) void scale_kernel(long long n, const T* __restrict__ pre, const T* __restrict__ r,
@@ -302,6 +326,7 @@ public:
             OPT_HIP_CHECK(hipMemsetAsync(red_.scalars + kScQ0, 0, sizeof(double), stream_));
         }
         OPT_HIP_CHECK(hipGetLastError());
+        schur_prepare(true);   // (delta_ = 0 here: the p of the reduced right-hand side's apply)
         if constexpr (HasBlockPre<Op>::value)
             if (block_) {   // M_e^-1 in place of the blocks, z_0 = M^-1 r, p_0 = z_0, rz_0
                 tbegin("blk_init");
@@ -315,6 +340,12 @@ public:
             pcg_loop(Lit, use_pre, stop);
             pcg_graph_end();
         }
+        if constexpr (HasSchur<Op>::value)
+            if (schur_ && Lit > 0) {   // delta_e = M^-1 (b_e - E^T delta_r); never skipped by LM's stop flag
+                tbegin("schur_back");
+                op_->schur_back(delta_, stream_);
+                tend();
+            }
         if (!lm_) {
             if (Lit > 0) update(false);
             precompute();
@@ -381,7 +412,7 @@ public:
                         done = true;
                     }
                 }
-                if (!done) {
+                if (!done && !schur_apply(p_, Ap_, lm_ ? CtC_ : nullptr, stop, red_.slot(nb(), pap(i)))) {
                     tbegin(Op::kApplyName);
                     op_->apply(p_, Ap_, lm_ ? CtC_ : nullptr, stop, red_.slot(nb(), pap(i)), stream_);
                     tend();
@@ -393,7 +424,8 @@ public:
                 hipLaunchKernelGGL((half1_kernel<T>), dim3(fg()), dim3(kBlock), 0, stream_, n_, (const T*)p_,
                                    delta_, red_.scalars, rz(i), pap(i), stop);
                 exchange_vec(delta_);
-                op_->apply(delta_, Adelta_, CtC_, stop, red_.slot(nb(), kScTmp), stream_);
+                if (!schur_apply(delta_, Adelta_, CtC_, stop, red_.slot(nb(), kScTmp)))
+                    op_->apply(delta_, Adelta_, CtC_, stop, red_.slot(nb(), kScTmp), stream_);
                 bool blk = false;
                 if constexpr (HasBlockPre<Op>::value)
                     if (block_) {
@@ -564,6 +596,7 @@ public:
             key.push_back((unsigned long long)(uintptr_t)blk_);
             key.push_back((unsigned long long)(uintptr_t)z_);
         }
+        if (schur_) key.push_back((unsigned long long)(uintptr_t)w_);
         if constexpr (!HasCaptureKey<Op>::value) {
             for (const DeclImage& im : spec_.images)   // arrays by address, scalars by value (below)
                 if (im.index >= 0 && im.index < spec_.n_params_total)
@@ -699,6 +732,7 @@ public:
                                    use_pre, lm, lo, hi, red_.slot(fg(), kScTmp));
         }
         OPT_HIP_CHECK(hipGetLastError());
+        schur_prepare(false);   // (a Schur plan's eliminated blocks: inverted by their own rule)
         bool blk = false;
         if constexpr (HasBlockPre<Op>::value)
             if (block_) {
@@ -712,6 +746,48 @@ public:
         OPT_HIP_CHECK(hipGetLastError());
         end_call();
         return 0;
+    }
+    int eliminated(int max_images, int* flag) const override {
+        for (int k = 0; k < L_.nimg && k < max_images; ++k)
+            if (flag) flag[k] = 0;
+        if constexpr (HasSchur<Op>::value)
+            if (schur_) return op_->eliminated(max_images, flag);
+        return L_.nimg;
+    }
+    // Sp = (B - E M^-1 E^T) p at the current unknowns (LM: with CtC_r p and M = C + CtC_e at the
+    // current radius), 0 in the eliminated entries, whatever the caller's p holds there: the
+    // same preparation as apply_preconditioner, then one reduced apply.
+    int apply_reduced(void** params, const void* pin, void* Sp) override {
+        if constexpr (HasSchur<Op>::value) {
+            if (!schur_) return 1;
+            begin_call();
+            prepare(params);
+            const int use_pre = spec_.use_preconditioner ? 1 : 0;
+            const long long lo = pix_lo(), hi = pix_hi();
+            red_.ensure(std::max(op_->stencil_blocks(), 4096), 4, kScBase + kSlots * (std::max(0, sp_.lIterations) + 2));
+            op_->jtf(r_, diag_, flags_, stream_);
+            if (!lm_) {
+                hipLaunchKernelGGL((gn_init_kernel<T>), dim3(fg()), dim3(kBlock), 0, stream_, L_, (const uint8_t*)flags_,
+                                   r_, (const T*)diag_, pre_, p_, use_pre, lo, hi, red_.slot(fg(), kScTmp));
+            } else {
+                LMScalars lm{initialised_ ? radius_ : sp_.trust_region_radius, sp_.min_lm_diagonal, sp_.max_lm_diagonal};
+                if (!initialised_ || n_iter_ == 0)
+                    hipLaunchKernelGGL((lm_init_kernel<T, true>), dim3(fg()), dim3(kBlock), 0, stream_, L_,
+                                       (const uint8_t*)flags_, r_, (const T*)diag_, SSq_, CtC_, pre_, b_, p_,
+                                       use_pre, lm, lo, hi, red_.slot(fg(), kScTmp));
+                else
+                    hipLaunchKernelGGL((lm_init_kernel<T, false>), dim3(fg()), dim3(kBlock), 0, stream_, L_,
+                                       (const uint8_t*)flags_, r_, (const T*)diag_, SSq_, CtC_, pre_, b_, p_,
+                                       use_pre, lm, lo, hi, red_.slot(fg(), kScTmp));
+            }
+            OPT_HIP_CHECK(hipGetLastError());
+            schur_prepare(false);
+            op_->block_init(r_, pre_, CtC_, z_, p_, lm_ ? 1 : 0, red_.slot(nb(), kScTmp), stream_);
+            schur_apply((const T*)pin, (T*)Sp, lm_ ? CtC_ : nullptr, nullptr, red_.slot(nb(), kScTmp));
+            end_call();
+            return 0;
+        }
+        return Plan::apply_reduced(params, pin, Sp);
     }
     int preconditioner_blocks(int max_images, int* group, int* first_row) const override {
         if constexpr (HasBlockPre<Op>::value)
@@ -799,6 +875,7 @@ public:
 
 private:
     static constexpr int kScCost = 1, kScModel = 0, kScTmp = 2, kScQ0 = 3, kScBase = 8;
+    static constexpr int kScQc = kScQ0 + 1;   // Schur plans: 1/2 b_e.M^-1 b_e, read as q0[1] by the exit test
     // cost sits right after model cost so one 16-byte copy (and one all-reduce) takes both
     // per PCG iteration: rz[i], q[i] (written together by step2 as a pair), pAp[i]
     // iteration i's slots: rz, q, pAp, then (fused PCG step) r.W Ap, Ap.W Ap, r.W r and
@@ -834,6 +911,17 @@ private:
                 op_->set_block_buffer(blk_);
             }
         }
+        if constexpr (HasSchur<Op>::value) {
+            schur_ = op_->schur();
+            if (schur_) {
+                const long long ne = op_->schur_entries();
+                w_ = (T*)dmalloc(sizeof(T) * ne);
+                be_ = (T*)dmalloc(sizeof(T) * ne);
+                OPT_HIP_CHECK(hipMemset(w_, 0, sizeof(T) * ne));
+                OPT_HIP_CHECK(hipMemset(be_, 0, sizeof(T) * ne));
+                op_->set_schur_buffers(w_, be_);
+            }
+        }
         flags_ = (uint8_t*)dmalloc(dom_.npix_mem());
         OPT_HIP_CHECK(hipMemset(flags_, 0, dom_.npix_mem()));
         red_.ensure(std::max(op_->stencil_blocks(), 4096), 2, 64);
@@ -845,7 +933,7 @@ private:
     }
     void release() {
         drop_graph();
-        for (T** v : {&r_, &diag_, &pre_, &p_, &Ap_, &delta_, &b_, &CtC_, &SSq_, &prev_, &Adelta_, &blk_, &z_}) {
+        for (T** v : {&r_, &diag_, &pre_, &p_, &Ap_, &delta_, &b_, &CtC_, &SSq_, &prev_, &Adelta_, &blk_, &z_, &w_, &be_}) {
             dfree(*v);
             *v = nullptr;
         }
@@ -853,6 +941,36 @@ private:
         flags_ = nullptr;
         mat_.reset();
         op_.reset();
+    }
+
+    // Schur plans, after the scalar init kernel and before block_init: M_e^-1 in place of the
+    // eliminated blocks, b_e stashed and cleared, 1/2 b_e.M^-1 b_e beside q0 (gen_blk_step2's exit
+    // test adds it); with `rhs` also r_r -= E M^-1 b_e (b_ too in LM) through one reduced apply
+    // of p = 0 — the caller's delta_, zeroed at the start of the step.
+    void schur_prepare(bool rhs) {
+        if constexpr (HasSchur<Op>::value)
+            if (schur_) {
+                tbegin("schur_rhs");
+                op_->schur_rhs(CtC_, r_, b_, lm_ ? 1 : 0, red_.slot(nb(), kScQc), stream_);
+                if (rhs) {
+                    op_->schur_apply(delta_, Ap_, nullptr, nullptr, red_.slot(nb(), kScTmp), stream_);
+                    hipLaunchKernelGGL((schur_sub_kernel<T>), dim3(fg()), dim3(kBlock), 0, stream_, n_, r_, (const T*)Ap_,
+                                       lm_ ? b_ : nullptr);
+                    OPT_HIP_CHECK(hipGetLastError());
+                }
+                tend();
+            }
+    }
+    // the reduced apply Ap = S p (two launches); false on a plan without Eliminate
+    bool schur_apply(const T* p, T* Ap, const T* dadd, const int* stop, ReduceSlot rs) {
+        if constexpr (HasSchur<Op>::value)
+            if (schur_) {
+                tbegin("schur_elim"); op_->schur_elim(p, stream_); tend();
+                tbegin("schur_apply"); op_->schur_apply(p, Ap, dadd, stop, rs, stream_); tend();
+                return true;
+            }
+        (void)p; (void)Ap; (void)dadd; (void)stop; (void)rs;
+        return false;
     }
 
     // bind + unknown halo + ComputedArrays, for the standalone entry points
@@ -968,6 +1086,8 @@ private:
     T *b_ = nullptr, *CtC_ = nullptr, *SSq_ = nullptr, *prev_ = nullptr, *Adelta_ = nullptr;
     bool block_ = false;                       // block preconditioner (HasBlockPre)
     T *blk_ = nullptr, *z_ = nullptr;          // its blocks (inverted in place) and z = M^-1 r
+    bool schur_ = false;                       // Eliminate: PCG on the Schur complement (HasSchur)
+    T *w_ = nullptr, *be_ = nullptr;           // compact (eliminated elements): M^-1-sized products, the stash of b_e
     uint8_t* flags_ = nullptr;
     int* stop_ = nullptr;
     hipGraphExec_t graph_exec_ = nullptr;      // captured PCG loop (pcg_graph_begin)
