@@ -211,12 +211,18 @@ int OptAMD_EvalJacobian(Opt_State* state, Opt_Plan* plan, void** problemparams,
 /* A^T of an nRowsA x nColsA matrix: rowPtrAT (nColsA+1), colIndAT and valAT (nnz), the
  * rows of A ascending inside each row of A^T (reference computeNnzPatternAT + computeAT,
  * API/src/linalg_cpu.t:203-297,512-551; cusparseScsr2csc, API/src/backend_cuda.t:600-612).
- * valA / valAT may be NULL (pattern only). */
+ * valA / valAT may be NULL (pattern only). The column indices of every row of A must be
+ * strictly ascending (no repeated column inside a row), the reference's contract for its
+ * CSR matrices: computeAT reads A(row, col) with getEntry, which takes the first match. */
 int OptAMD_CsrTranspose(int nRowsA, int nColsA, long long nnz, const int* rowPtrA,
                         const int* colIndA, const void* valA, int* rowPtrAT, int* colIndAT,
                         void* valAT, int doublePrecision);
 
-/* A^T A (nColsA x nColsA) of A with sorted columns in every row. First call with
+/* A^T A (nColsA x nColsA) of A. The column indices of every row of A must be strictly
+ * ascending: sorted, and no column repeated inside a row. This is the reference's
+ * contract (computeATA walks each row of A once against the sorted A^T A row, so a
+ * repeated or out-of-order column, and every entry of the row after it, is dropped from
+ * the sums); nothing checks it. First call with
  * colIndATA = valATA = NULL: fills rowPtrATA (nColsA+1) and *nnzATA; second call with
  * those arrays allocated: sorted column indices and the values, each summed over the
  * rows of A in ascending order (reference computeNnzPatternATA + computeATA,

@@ -709,6 +709,7 @@ public:
         const unsigned long long h = graph_fingerprint(vs, 2, E_, s, fp_scratch_);
         if (v0 != graph_v0_ || v1 != graph_v1_ || h != fingerprint_) {
             build_csr(v0, v1, s);
+            if (h != fingerprint_) ++topology_generation_;   // other content, not merely another address
             fingerprint_ = h;
         }
         a_.N = N_;
@@ -767,6 +768,8 @@ public:
     // per directed edge (5 + 5 + 4 nonzeros)
     long long jacobian_rows() const { return 3LL * N_ + 3LL * E_; }
     long long jacobian_nnz() const { return 3LL * N_ + 14LL * E_; }
+    // bumped when bind finds other edges (stencil_plan.h, HasTopologyGeneration)
+    unsigned long long topology_generation() const { return topology_generation_; }
     void dump_j(int* rowPtr, int* colInd, T* val, hipStream_t s) {
         hipLaunchKernelGGL((arap::arap_dump_fit<T>), dim3(std::max(1, std::min((N_ + 255) / 256, 4096))), dim3(kBlock),
                            0, s, a_, E_, rowPtr, colInd, val);
@@ -903,6 +906,7 @@ private:
     const int* graph_v0_ = nullptr;
     const int* graph_v1_ = nullptr;
     unsigned long long fingerprint_ = 0;
+    unsigned long long topology_generation_ = 0;
     unsigned long long* fp_scratch_ = (unsigned long long*)dmalloc(sizeof(unsigned long long) * (1 + kFingerprintGrid));
     void* scratch_ = nullptr;
     size_t scratch_bytes_ = 0;

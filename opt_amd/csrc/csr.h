@@ -13,8 +13,10 @@
 // column indices (hipCUB) — rows of A stay ascending inside every row of A^T, exactly
 // the csr2csc / computeNnzPatternAT order — which also yields a gather map, so the
 // per-step value transpose is one coalesced gather. The A^T A pattern is built once
-// per plan (one thread per row, sorted-unique merge of the A rows the A^T row
-// touches); its values are recomputed every step in the reference's summation order
+// per sparsity structure of J (one thread per row, sorted-unique merge of the A rows the
+// A^T row touches) — once per plan for image energies, again whenever a graph energy's
+// vertex arrays change (drop_patterns below); its values are recomputed every step in
+// the reference's summation order
 // (rows of A ascending), so they match the CPU restatement bit for bit. The solver's
 // SpMVs run over a SELL-64 copy of each operator (slices of 64 rows = one wavefront,
 // column-major inside the slice): lane r owns row r, every load instruction is one
@@ -84,10 +86,6 @@ struct PcgMask {
     long long pix_lo, pix_hi;
     const int* stop;
 };
-int csr_pcg_blocks(int rows);
-template <typename T>
-void csr_spmv_pcg(int rows, long long nnz, const int* rowPtr, const int* colInd, const T* val, const T* x, T* y,
-                  const T* pv, const PcgMask& m, ReduceSlot rs, hipStream_t s);
 
 // SELL-64 (the solver's SpMV layout): rows in slices of 64 = one wavefront, slice
 // width = its longest row, entries column-major inside a slice so lane r of the wave
@@ -112,11 +110,6 @@ void sell_build(int rows, const int* rowPtr, const int* colInd, SellMatrix& S, D
 void sell_compose(SellMatrix& S, const int* perm, hipStream_t s);
 template <typename T>
 void sell_values(const SellMatrix& S, const T* csrVal, T* sellVal, hipStream_t s);
-// computeATA straight into the SELL layout of the A^T A pattern (bitwise computeATA)
-template <typename T>
-void ata_values_sell(int cols, const int* rowPtrA, const int* colIndA, const T* valA, const int* rowPtrT,
-                     const int* colIndT, const T* valT, const int* rowPtrATA, const int* colIndATA,
-                     const SellMatrix& S, T* sellVal, hipStream_t s);
 int sell_blocks(const SellMatrix& S);
 
 // A^T A product map (the solver's per-step J^T J): for every slot of the A^T A SELL-64
@@ -149,8 +142,9 @@ template <typename T>
 void sell_spmv_pcg(const SellMatrix& S, const T* val, const T* x, T* y, const T* pv, const PcgMask& m, ReduceSlot rs,
                    hipStream_t s);
 
-// The solver-side holder: J (filled by the family's dump_j), J^T (pattern once, values
-// every step), J^T J (fused only), the SELL-64 copies the SpMVs stream, and the apply.
+// The solver-side holder: J (filled by the family's dump_j), J^T (pattern once per
+// sparsity structure, values every step), J^T J (fused only), the SELL-64 copies the
+// SpMVs stream, and the apply.
 template <typename T>
 class MaterializedJacobian {
 public:
@@ -193,11 +187,34 @@ public:
     int blocks() const { return sell_blocks(fused_ ? sA_ : sT_); }
     const char* apply_name() const { return fused_ ? "J^TJp" : "J^T"; }
 
-    // After the family filled J: the patterns once (section 1 of cusparseOuter,
-    // :1563-1620), then J^T values (+ J^T J values when fused) (section 2, :1623-1656).
+    // Everything derived from J's sparsity structure (the J^T pattern and gather map are
+    // overwritten in place; the J^T J pattern, the SELL copies, their value arrays and the
+    // product map are freed): the next build() derives it again from the J then assembled.
+    // For the plan to call when the column structure of J changes — a graph energy whose
+    // vertex arrays were rewritten or rebound between two Steps (stencil_plan.h,
+    // HasTopologyGeneration). blocks() and every buffer address change with it.
+    void drop_patterns() {
+        for (T** v : {&svJ_, &svT_, &svA_}) {
+            dfree(*v);
+            *v = nullptr;
+        }
+        dfree(colIndATA_);
+        colIndATA_ = nullptr;
+        sJ_.release();
+        sT_.release();
+        sA_.release();
+        prod_.release();
+        nnz_ata_ = 0;
+        patterns_ = false;
+    }
+
+    // After the family filled J: the patterns once per sparsity structure (section 1 of
+    // cusparseOuter, :1563-1620), then J^T values (+ J^T J values when fused) (section 2,
+    // :1623-1656).
     template <class Timer>
     void build(Timer&& tb, hipStream_t s) {
         if (!patterns_) {
+            drop_patterns();   // nothing of an earlier structure outlives this build
             tb("JT alloc", true);
             csr_transpose_pattern(rows_, cols_, nnz_, rowPtrJ_, colIndJ_, rowPtrT_, colIndT_, perm_, scratch_, s);
             if (!fused_) {

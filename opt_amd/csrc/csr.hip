@@ -142,24 +142,20 @@ __global__ __launch_bounds__(kBlock) void sum_counts(int n, const int* __restric
 // WMAX-wide register arrays (unrolled compare-select, no dynamic indexing); every
 // product t * A(r, c) is rounded and added to its column's accumulator in the order of
 // the reference loop, so the result is bitwise that of computeATA. Rows longer than
-// WMAX take the merge loop above. sliceOff != nullptr writes the SELL-64 layout of the
-// A^T A pattern (sell_* below) instead of CSR.
+// WMAX take the reference's merge loop, which needs strictly ascending columns in every
+// row of A (include/opt_amd.h, OptAMD_CsrATA).
 template <typename T, int WMAX>
 __global__ __launch_bounds__(kBlock) void ata_values_reg(int cols, const int* __restrict__ rowPtrA,
                                                          const int* __restrict__ colIndA, const T* __restrict__ valA,
                                                          const int* __restrict__ rowPtrT,
                                                          const int* __restrict__ colIndT, const T* __restrict__ valT,
                                                          const int* __restrict__ rowPtrATA,
-                                                         const int* __restrict__ colIndATA, T* __restrict__ valATA,
-                                                         const int* __restrict__ sliceOff) {
+                                                         const int* __restrict__ colIndATA, T* __restrict__ valATA) {
 #pragma clang fp contract(off)
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < cols; i += gridDim.x * blockDim.x) {
         const int b = rowPtrATA[i], n = rowPtrATA[i + 1] - b;
-        // output position of the row's l-th entry
-        const long long ob = sliceOff ? (long long)sliceOff[i >> 6] + (i & 63) : b;
-        const int os = sliceOff ? 64 : 1;
         if (n > WMAX) {
-            for (int l = 0; l < n; ++l) valATA[ob + (long long)l * os] = (T)0;
+            for (int l = 0; l < n; ++l) valATA[b + l] = (T)0;
             for (int k = rowPtrT[i]; k < rowPtrT[i + 1]; ++k) {
                 const T t = valT[k];
                 const int r = colIndT[k];
@@ -167,8 +163,7 @@ __global__ __launch_bounds__(kBlock) void ata_values_reg(int cols, const int* __
                 const int ce = rowPtrA[r + 1];
                 for (int l = 0; l < n && ci < ce; ++l) {
                     if (colIndATA[b + l] == colIndA[ci]) {
-                        const long long o = ob + (long long)l * os;
-                        valATA[o] = valATA[o] + t * valA[ci];
+                        valATA[b + l] = valATA[b + l] + t * valA[ci];
                         ++ci;
                     }
                 }
@@ -195,7 +190,7 @@ __global__ __launch_bounds__(kBlock) void ata_values_reg(int cols, const int* __
         }
 #pragma unroll
         for (int l = 0; l < WMAX; ++l)
-            if (l < n) valATA[ob + (long long)l * os] = acc[l];
+            if (l < n) valATA[b + l] = acc[l];
     }
 }
 
@@ -407,61 +402,17 @@ __global__ __launch_bounds__(kBlock) void sell_spmv(int rows, int nslices, const
     }
 }
 
+// y = A x, one lane per row: entries in order with rounded products.
 template <typename T>
-__device__ __forceinline__ T group_sum(T v, int G) {
-    for (int off = G >> 1; off > 0; off >>= 1) v += __shfl_xor(v, off, G);
-    return v;
-}
-
-// y = A x with G lanes per row.
-template <typename T, int G>
 __global__ __launch_bounds__(kBlock) void spmv(int rows, const int* __restrict__ rowPtr,
                                                const int* __restrict__ colInd, const T* __restrict__ val,
                                                const T* __restrict__ x, T* __restrict__ y) {
 #pragma clang fp contract(off)
-    const int lg = threadIdx.x & (G - 1);
-    const long long ngroups = (long long)gridDim.x * (kBlock / G);
-    for (long long r = ((long long)blockIdx.x * kBlock + threadIdx.x) / G; r < rows; r += ngroups) {
-        const int b = rowPtr[r], e = rowPtr[r + 1];
+    for (long long r = (long long)blockIdx.x * kBlock + threadIdx.x; r < rows; r += (long long)gridDim.x * kBlock) {
         T acc = 0;
-        for (int k = b + lg; k < e; k += G) acc = acc + x[colInd[k]] * val[k];
-        acc = group_sum(acc, G);
-        if (lg == 0) y[r] = acc;
+        for (int k = rowPtr[r]; k < rowPtr[r + 1]; ++k) acc = acc + x[colInd[k]] * val[k];
+        y[r] = acc;
     }
-}
-
-// PCG variant: masked output + sum pv.y (deterministic block reduction).
-template <typename T, int G>
-__global__ __launch_bounds__(kBlock) void spmv_pcg(int rows, const int* __restrict__ rowPtr,
-                                                   const int* __restrict__ colInd, const T* __restrict__ val,
-                                                   const T* __restrict__ x, T* __restrict__ y,
-                                                   const T* __restrict__ pv, PcgMask m, ReduceSlot rs) {
-    if (stopped(m.stop)) return;
-    const int lg = threadIdx.x & (G - 1);
-    const long long ngroups = (long long)gridDim.x * (kBlock / G);
-    T dot = 0;
-    for (long long r = ((long long)blockIdx.x * kBlock + threadIdx.x) / G; r < rows; r += ngroups) {
-        const int b = rowPtr[r], e = rowPtr[r + 1];
-        T acc = 0;
-        for (int k = b + lg; k < e; k += G) acc += val[k] * x[colInd[k]];
-        acc = group_sum(acc, G);
-        if (lg == 0) {
-            const long long px = m.L.pix(r);
-            const bool act = px >= m.pix_lo && px < m.pix_hi && (m.flags[px] & 1);
-            if (!act) acc = 0;
-            y[r] = acc;
-            dot += pv[r] * acc;
-        }
-    }
-    double v[1] = {(double)dot};
-    block_reduce_publish<1>(v, rs, blockIdx.x);
-}
-
-inline int group_for(long long rows, long long nnz) {
-    const double avg = rows > 0 ? (double)nnz / (double)rows : 1.0;
-    int G = 1;
-    while (G < 16 && G < avg) G <<= 1;
-    return G;
 }
 
 }  // namespace csr
@@ -600,7 +551,7 @@ void csr_ata_values(int cols, const int* rowPtrA, const int* colIndA, const T* v
                     const int* colIndT, const T* valT, const int* rowPtrATA, const int* colIndATA, T* valATA,
                     hipStream_t s) {
     hipLaunchKernelGGL((csr::ata_values_reg<T, 16>), dim3(csr::grid_for(cols)), dim3(kBlock), 0, s, cols, rowPtrA,
-                       colIndA, valA, rowPtrT, colIndT, valT, rowPtrATA, colIndATA, valATA, (const int*)nullptr);
+                       colIndA, valA, rowPtrT, colIndT, valT, rowPtrATA, colIndATA, valATA);
     OPT_HIP_CHECK(hipGetLastError());
 }
 
@@ -610,28 +561,8 @@ void csr_spmv(int rows, long long nnz, const int* rowPtr, const int* colInd, con
     // one lane per row, entries in order with rounded products: bitwise applyAtoVector
     if (rows == 0) return;
     (void)nnz;
-    hipLaunchKernelGGL((csr::spmv<T, 1>), dim3(csr::grid_for(rows)), dim3(kBlock), 0, s, rows, rowPtr, colInd, val, x,
+    hipLaunchKernelGGL((csr::spmv<T>), dim3(csr::grid_for(rows)), dim3(kBlock), 0, s, rows, rowPtr, colInd, val, x,
                        y);
-    OPT_HIP_CHECK(hipGetLastError());
-}
-
-int csr_pcg_blocks(int rows) { return csr::grid_for((long long)rows * 16); }
-
-template <typename T>
-void csr_spmv_pcg(int rows, long long nnz, const int* rowPtr, const int* colInd, const T* val, const T* x, T* y,
-                  const T* pv, const PcgMask& m, ReduceSlot rs, hipStream_t s) {
-    // the grid is fixed by csr_pcg_blocks (the reduction slot's block count)
-    const int G = csr::group_for(rows, nnz);
-    const dim3 g(csr_pcg_blocks(rows)), b(kBlock);
-#define SPMV(GG) hipLaunchKernelGGL((csr::spmv_pcg<T, GG>), g, b, 0, s, rows, rowPtr, colInd, val, x, y, pv, m, rs)
-    switch (G) {
-        case 1: SPMV(1); break;
-        case 2: SPMV(2); break;
-        case 4: SPMV(4); break;
-        case 8: SPMV(8); break;
-        default: SPMV(16); break;
-    }
-#undef SPMV
     OPT_HIP_CHECK(hipGetLastError());
 }
 
@@ -673,17 +604,6 @@ void sell_values(const SellMatrix& S, const T* csrVal, T* sellVal, hipStream_t s
     if (S.padded == 0) return;
     hipLaunchKernelGGL((csr::sell_gather<T>), dim3(csr::grid_for(S.padded)), dim3(kBlock), 0, s, S.padded,
                        (const int*)S.pos, csrVal, sellVal);
-    OPT_HIP_CHECK(hipGetLastError());
-}
-template <typename T>
-void ata_values_sell(int cols, const int* rowPtrA, const int* colIndA, const T* valA, const int* rowPtrT,
-                     const int* colIndT, const T* valT, const int* rowPtrATA, const int* colIndATA,
-                     const SellMatrix& S, T* sellVal, hipStream_t s) {
-    if (S.padded == 0) return;
-    OPT_HIP_CHECK(hipMemsetAsync(sellVal, 0, sizeof(T) * S.padded, s));   // padding stays 0
-    hipLaunchKernelGGL((csr::ata_values_reg<T, 16>), dim3(csr::grid_for(cols)), dim3(kBlock), 0, s, cols, rowPtrA,
-                       colIndA, valA, rowPtrT, colIndT, valT, rowPtrATA, colIndATA, sellVal,
-                       (const int*)S.sliceOff);
     OPT_HIP_CHECK(hipGetLastError());
 }
 void ata_products_build(int cols, const int* rowPtrA, const int* colIndA, const int* rowPtrT, const int* colIndT,
@@ -762,11 +682,7 @@ void sell_spmv_pcg(const SellMatrix& S, const T* val, const T* x, T* y, const T*
     template void csr_ata_values<T>(int, const int*, const int*, const T*, const int*, const int*, const T*,     \
                                     const int*, const int*, T*, hipStream_t);                                    \
     template void csr_spmv<T>(int, long long, const int*, const int*, const T*, const T*, T*, hipStream_t);      \
-    template void csr_spmv_pcg<T>(int, long long, const int*, const int*, const T*, const T*, T*, const T*,      \
-                                  const PcgMask&, ReduceSlot, hipStream_t);                                   \
     template void sell_values<T>(const SellMatrix&, const T*, T*, hipStream_t);                                 \
-    template void ata_values_sell<T>(int, const int*, const int*, const T*, const int*, const int*, const T*,    \
-                                     const int*, const int*, const SellMatrix&, T*, hipStream_t);                \
     template void sell_spmv<T>(const SellMatrix&, const T*, const T*, T*, hipStream_t);                         \
     template void ata_values_products<T>(const AtaProducts&, const T*, T*, hipStream_t);                        \
     template void sell_spmv_pcg<T>(const SellMatrix&, const T*, const T*, T*, const T*, const PcgMask&,          \

@@ -590,6 +590,8 @@ public:
         }
         OPT_HIP_CHECK(hipMemsetD32Async(rowPtr + rb, (int)zb, 1, s));
     }
+    // the graphs' vertex arrays changed (check_graphs; stencil_plan.h, HasTopologyGeneration)
+    unsigned long long topology_generation() const { return topology_generation_; }
 
     const std::string& source() const { return src_.code; }
     bool tiled_selected() const { return k_apply_ == k_apply_tiled_; }
@@ -751,6 +753,7 @@ private:
                         }
                 }
                 fingerprint_[g] = h;
+                ++topology_generation_;
                 for (int k = 0; k < ns; ++k) build_incidence(sb + k, nedge_[g], slot_pixels(g, k), s);
                 for (int k = 0; k < ns; ++k) build_neighbours(sb + k, nedge_[g], s);
             }
@@ -826,6 +829,7 @@ private:
     void* dimg_[16] = {};
     int* dslot_[16] = {};
     unsigned long long fingerprint_[4] = {0, 0, 0, 0};
+    unsigned long long topology_generation_ = 0;   // bumped with every rebuild of the incidence lists
     unsigned long long* fp_scratch_ = nullptr;
     int* goff_[16] = {};
     int* geid_[16] = {};

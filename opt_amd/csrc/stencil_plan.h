@@ -166,6 +166,20 @@ template <class Op>
 struct HasRefreshCaches<Op, std::void_t<decltype(std::declval<Op&>().refresh_caches(hipStream_t{}))>>
     : std::true_type {};
 
+// Ops whose Jacobian's column structure comes from bound vertex arrays (ArapOp, GenericOp
+// with graphs): topology_generation() is a counter the Op bumps whenever bind finds the
+// arrays' content fingerprint changed and rebuilds its incidence lists (graph_util.h). The
+// materialized path keeps everything it derives from J's sparsity (J^T pattern, J^T J
+// pattern, SELL copies, product map) for as long as that counter stands, and derives it
+// again at the first Step or apply after it moved (materialize below): the Step-boundary
+// contract lets a caller rewrite or rebind the vertex arrays between Steps. Image families
+// have no such method and build their patterns once per plan.
+template <class Op, class = void>
+struct HasTopologyGeneration : std::false_type {};
+template <class Op>
+struct HasTopologyGeneration<Op, std::void_t<decltype(std::declval<const Op&>().topology_generation())>>
+    : std::true_type {};
+
 // Ops that describe their own hipGraph capture gate and key (GenericOp: the kernel
 // argument block the generated launches receive) instead of the declaration parser's.
 template <class Op, class = void>
@@ -1062,6 +1076,16 @@ private:
     // J at the current unknowns (saveJToCRS), then J^T (+ J^T J) values (cusparseOuter)
     void materialize() {
         if constexpr (HasDumpJ<Op>::value) {
+            if constexpr (HasTopologyGeneration<Op>::value) {
+                // a re-wired graph: patterns of the old wiring are in range but wrong; their
+                // buffers and the apply's grid change, so no captured loop survives either
+                const unsigned long long gen = op_->topology_generation();
+                if (gen != mat_generation_) {
+                    mat_->drop_patterns();
+                    drop_graph();
+                    mat_generation_ = gen;
+                }
+            }
             tbegin("saveJToCRS");
             op_->dump_j(mat_->rowPtrJ(), mat_->colIndJ(), mat_->valJ(), stream_);
             tend();
@@ -1104,6 +1128,7 @@ private:
     const int fuse23_ = env_int("OPT_AMD_FUSE23", 2);
     const bool delta3_on_ = env_int("OPT_AMD_DELTA_IN_STEP3", 1) != 0;   // 0: delta updated by step2    // 0: step3_kernel + the whole apply
     std::unique_ptr<MaterializedJacobian<T>> mat_;
+    unsigned long long mat_generation_ = 0;    // Op::topology_generation() mat_'s patterns were built for
     float radius_ = 1e4f, decrease_ = 2.0f;
 };
 

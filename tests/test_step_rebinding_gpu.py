@@ -25,6 +25,12 @@ That a path ignoring a mutation cannot pass is asserted from the oracle alone: t
 without the mutations differs from the replay with them by at least 1e-2 relative in the
 cost of every step after the first mutation.
 
+Materialized plans (useMaterializedJTJ, with and without useFusedJTJ) run the ARAP row in
+fp64 as well: its mutation before step 2 re-wires v0 / v1, which changes the column
+structure of J and with it every pattern csr.h derives from J (StencilPlan::materialize
+rebuilds them when the Op's topology generation moves). Those rows first run the unmutated
+solve against the unmutated replay at the same bars, as a control of the path itself.
+
 shape_from_shading: only w_p / w_s / w_g, edgeMaskR / edgeMaskC and the values of D_i
 where it is already > 0 (kept > 0) are mutated — weights before step 1, edge masks before
 step 2, D_i before step 3. X, Im, the signs of D_i, f_*, u_* and L_* feed the ComputedArrays
@@ -337,12 +343,16 @@ def _apply_solver(case, prm, ops, how, kept):
             prm[i] = v
 
 
-def _run(case, double, how, host=False, kind="gaussNewtonGPU", family=None, trial=None):
-    """init + NSTEPS steps with the case's mutations; (costs, {unknown: final values})."""
+def _run(case, double, how, host=False, kind="gaussNewtonGPU", family=None, trial=None, mat=None, mutate=True):
+    """init + NSTEPS steps with the case's mutations (none with mutate=False); (costs,
+    {unknown: final values}). mat: None for a matrix-free plan, "fused" / "unfused" for a
+    materialized one (useMaterializedJTJ with / without useFusedJTJ)."""
     import torch
 
     s = OptSolver(case.dims, case.energy, kind, double_precision=double,
-                  backend="backend_cpu" if host else "backend_cuda")
+                  backend="backend_cpu" if host else "backend_cuda",
+                  materialized=mat is not None, fused_jtj=mat == "fused")
+    assert (s.materialized_nonzeros() is not None) == (mat is not None)
     assert s.family() == (family or case.family)
     s.set_solver_params({"nIterations": NSTEPS, "lIterations": LIT})
     w = case.base()
@@ -352,7 +362,7 @@ def _run(case, double, how, host=False, kind="gaussNewtonGPU", family=None, tria
     costs, kept = [], []
     for k in range(NSTEPS):
         # the mutation's values come from the case's own base arrays, not from the solver
-        ops = case.mutation(k, w)
+        ops = case.mutation(k, w) if mutate else []
         _apply_oracle(case, w, [o for o in ops if o[0] not in case.unknowns], double)
         if ops:
             _apply_solver(case, prm, ops, how, kept)
@@ -361,7 +371,7 @@ def _run(case, double, how, host=False, kind="gaussNewtonGPU", family=None, tria
         if trial is not None:   # LM: the step's model cost and the cost at its trial point
             trial.append(s.scalars(2))
     now = [p.data_ptr() for p in prm if isinstance(p, torch.Tensor)]
-    if how == "in_place":
+    if how == "in_place" or not mutate:
         assert now == ptrs   # every update was in place
     else:
         assert not host and all(a != b for a, b in zip(now, ptrs))
@@ -384,22 +394,47 @@ def _check(case, cname, double, costs, unk):
         assert udrift[u] <= ubar[u], (u, udrift[u], ubar[u])
 
 
-ROWS = [(c, gen, dbl)
+ROWS = [(c, gen, dbl, None)
         for c, paths, dbls in (("of64x48", (True, False), (False, True)), ("of130x7", (True, False), (False, True)),
                                ("pie64x48", (False, True), (False, True)), ("sfs97x61", (False, True), (False, True)),
                                ("arap20x13", (False,), (False, True)))
         for gen in paths for dbl in dbls]
+# ARAP on materialized plans (fp64): the mutation before step 2 re-wires v0 / v1, and J's
+# column structure — hence the J^T and J^T J patterns, the SELL copies and the product map
+# of csr.h — comes from those arrays
+ROWS += [("arap20x13", False, True, m) for m in ("fused", "unfused")]
+
+
+@functools.lru_cache(maxsize=None)
+def _materialized_control(cname, double, mat):
+    """The unmutated solve on a materialized plan against the unmutated oracle replay, at
+    the family's own bars: the materialized path itself agrees with the (matrix-free)
+    oracle before anything is re-wired. Once per plan kind."""
+    case = CASES[cname]
+    costs, unk = _run(case, double, "in_place", mat=mat, mutate=False)
+    ref, wo = _replay(case, double, mutate=False)
+    drift = np.abs(costs - ref) / ref
+    udrift = {u: _err(u, unk[u], wo[u], double) for u in case.unknowns}
+    print(f"{cname} double={double} materialized {mat}, no mutation: cost drift {drift}, unknowns {udrift}")
+    return drift, udrift
 
 
 @pytest.mark.parametrize("how", ["in_place", "rebind"])
-@pytest.mark.parametrize("cname,generated,double", ROWS,
-                         ids=[f"{c}-{'generated' if g else 'handwritten'}-{'fp64' if d else 'fp32'}" for c, g, d in ROWS])
-def test_arrays_changed_between_steps_match_oracle(monkeypatch, cname, generated, double, how):
-    """See the module docstring (mutations, bars, the shape_from_shading restriction)."""
+@pytest.mark.parametrize("cname,generated,double,mat", ROWS,
+                         ids=[f"{c}-{'generated' if g else 'handwritten'}-{'fp64' if d else 'fp32'}"
+                              + (f"-materialized-{m}" if m else "") for c, g, d, m in ROWS])
+def test_arrays_changed_between_steps_match_oracle(monkeypatch, cname, generated, double, mat, how):
+    """See the module docstring (mutations, bars, the shape_from_shading restriction). The
+    materialized rows first hold the unmutated solve to the same bars (the control)."""
     if generated:
         monkeypatch.setenv("OPT_AMD_GENERIC", "1")
     case = CASES[cname]
-    costs, unk = _run(case, double, how, family="generic" if generated else None)
+    if mat:
+        drift, udrift = _materialized_control(cname, double, mat)
+        assert np.all(drift <= case.cost_tol[double]), drift
+        for u in case.unknowns:
+            assert udrift[u] <= case.unk_tol[double][u], (u, udrift[u])
+    costs, unk = _run(case, double, how, family="generic" if generated else None, mat=mat)
     _check(case, cname, double, costs, unk)
 
 
