@@ -103,6 +103,36 @@ int OptAMD_PlanEliminated(Opt_Plan* plan, int maxImages, int* eliminated);
 int OptAMD_ApplyReduced(Opt_State* state, Opt_Plan* plan, void** problemparams,
                         const void* p, void* Sp);
 
+/* The explicitly formed reduced system: ReducedSystem("explicit") beside Eliminate makes the
+ * plan assemble S once per Step in block-CSR (blocks of blockDim x blockDim, blockDim the
+ * retained element's channel count, row-major inside a block; rows and columns are retained
+ * elements, columns ascending, every diagonal block present) and run PCG's apply as a block
+ * SpMV. LM's retained diagonal is not part of S (the apply adds it). The pattern follows the
+ * graphs' vertex arrays as bound and is rebuilt when they are re-wired between Steps.
+ * ReducedSystem("implicit"), or no statement, is the matrix-free apply. Shapes the explicit
+ * form does not take are refused by Opt_ProblemPlan by name.
+ *
+ * Returns 1 and the shape on an explicit plan once the graphs have been bound (by Init, Step,
+ * or any entry point that takes problemparams), 0 on any other plan or before, -1 for NULL. */
+int OptAMD_PlanReducedMatrixShape(Opt_Plan* plan, long long* blockRows, int* blockDim, long long* nnzBlocks);
+
+/* S assembled at the bound unknowns (on an LMGPU plan with M at the plan's current
+ * trust-region radius), copied into caller device arrays: rowPtr blockRows + 1, colInd
+ * nnzBlocks, val nnzBlocks * blockDim^2 in the plan's precision. With all three NULL the call
+ * binds the arrays and builds the pattern only, so that OptAMD_PlanReducedMatrixShape can size
+ * them. Returns 0, or 1 on a plan without an explicit reduced system. */
+int OptAMD_ReducedMatrix(Opt_Plan* plan, void** problemparams, int* rowPtr, int* colInd, void* val);
+
+/* The symbolic phase behind that pattern, on the host from index arrays alone (no device):
+ * list l has nEdges[l] edge instances with eliminated vertex elimVertex[l][e] and retained
+ * vertex retVertex[l][e]. Instance positions: list after list, each list ordered by eliminated
+ * vertex, ties by edge index. Every output may be NULL; counts receives {instances, pairs,
+ * blocks}; pairPtr has blocks + 1 entries and pairs two positions (q1, q2) per pair. Returns 0,
+ * or -1 with the cause in buf (an index outside its space, more than 2^31 - 1 pairs). */
+int OptAMD_SchurPattern(long long nEliminated, long long nRetained, int nLists, const int* const* elimVertex,
+                        const int* const* retVertex, const long long* nEdges, long long* counts, int* rowPtr,
+                        int* colInd, int* pairPtr, int* pairs, char* buf, int buflen);
+
 /* Ap = J^T J p at the current unknowns (+ CtC*p for LM plans, with the CtC of the
  * last LM step) and *p_dot_Ap = p.Ap (reference kernels.PCGStep1,
  * solverGPUGaussNewton.t:607-632, with fmap.applyJTJ o.t:2770-2830). Excluded
@@ -244,6 +274,11 @@ int OptAMD_CsrSpMV(int nRowsA, int nColsA, long long nnz, const int* rowPtrA, co
  * to n). Returns the full length, or -1 with the front end's message in buf. No device
  * needed. */
 int OptAMD_GenericSource(const char* filename, int doublePrecision, char* buf, int n);
+
+/* The checks Opt_ProblemPlan makes on the lowered energy before it asks for a device (the
+ * shapes ReducedSystem("explicit") takes). 0 accepted, 1 refused with the plan's message in
+ * buf, -1 with the front end's message if the file does not lower. No device needed. */
+int OptAMD_GenericPlanCheck(const char* filename, char* buf, int n);
 
 /* The residual templates the front end lowered `filename` to, one line each:
  * "<centred|graphK> <number of unknowns it reads> <expression>" (the reference's

@@ -98,6 +98,14 @@ _SIGNATURES = [
                                       ctypes.c_int]),
     ("OptAMD_GenericSource", ctypes.c_int, [ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]),
     ("OptAMD_GenericDescribe", ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int]),
+    ("OptAMD_GenericPlanCheck", ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int]),
+    ("OptAMD_PlanReducedMatrixShape", ctypes.c_int, [_VP, ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_int),
+                                                     ctypes.POINTER(ctypes.c_longlong)]),
+    ("OptAMD_ReducedMatrix", ctypes.c_int, [_VP, ctypes.POINTER(_VP), _VP, _VP, _VP]),
+    ("OptAMD_SchurPattern", ctypes.c_int, [ctypes.c_longlong, ctypes.c_longlong, ctypes.c_int, ctypes.POINTER(_VP),
+                                           ctypes.POINTER(_VP), ctypes.POINTER(ctypes.c_longlong),
+                                           ctypes.POINTER(ctypes.c_longlong), _VP, _VP, _VP, _VP, ctypes.c_char_p,
+                                           ctypes.c_int]),
     ("OptAMD_GenericCompileCheck", ctypes.c_int, [ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]),
 ]
 EXPORTED_SYMBOLS = [s[0] for s in _SIGNATURES]
@@ -324,6 +332,34 @@ class OptSolver:
             self._raise_plan_error()
             raise OptError("OptAMD_ApplyReduced failed (a plan without Eliminate has no reduced system)")
 
+    def reduced_matrix_shape(self):
+        """(block rows, block dimension, blocks) of the explicitly formed S once the graphs
+        are bound (OptAMD_PlanReducedMatrixShape); None on any other plan, or before."""
+        rows, dim, nnzb = ctypes.c_longlong(), ctypes.c_int(), ctypes.c_longlong()
+        k = self.lib.OptAMD_PlanReducedMatrixShape(self.plan, ctypes.byref(rows), ctypes.byref(dim), ctypes.byref(nnzb))
+        if k < 0:
+            raise OptError("OptAMD_PlanReducedMatrixShape failed")
+        return (rows.value, dim.value, nnzb.value) if k == 1 else None
+
+    def reduced_matrix(self, problem_params):
+        """S = B - E M^-1 E^T assembled at the bound unknowns, in block-CSR (OptAMD_ReducedMatrix
+        on a plan whose energy has ReducedSystem("explicit")): (rowPtr, colInd, val[nnzb, C, C])
+        as torch tensors on the plan's device."""
+        import torch
+        pk = ParamPack(problem_params)
+        if self.lib.OptAMD_ReducedMatrix(self.plan, pk.ptr, None, None, None):
+            self._raise_plan_error()
+            raise OptError("OptAMD_ReducedMatrix failed (the plan has no explicit reduced system)")
+        rows, dim, nnzb = self.reduced_matrix_shape()
+        row_ptr = torch.empty(rows + 1, dtype=torch.int32, device="cuda")
+        col_ind = torch.empty(max(nnzb, 1), dtype=torch.int32, device="cuda")
+        val = torch.empty((max(nnzb, 1), dim, dim), dtype=torch.float64 if self.double_precision else torch.float32,
+                          device="cuda")
+        if self.lib.OptAMD_ReducedMatrix(self.plan, pk.ptr, _ptr(row_ptr), _ptr(col_ind), _ptr(val)):
+            self._raise_plan_error()
+            raise OptError("OptAMD_ReducedMatrix failed")
+        return row_ptr, col_ind[:nnzb], val[:nnzb]
+
     def eval_cost(self, problem_params) -> float:
         pk = ParamPack(problem_params)
         c = self.lib.OptAMD_EvalCost(self.state, self.plan, pk.ptr)
@@ -486,6 +522,40 @@ def generic_signature(energy_file: str) -> str:
     if r < 0:
         raise OptError(txt)
     return txt
+
+
+def generic_plan_check(energy_file: str) -> str:
+    """The shape checks Opt_ProblemPlan makes before it asks for a device
+    (OptAMD_GenericPlanCheck): '' if the plan would accept the energy, else its refusal."""
+    r, txt = _text_call(load_library().OptAMD_GenericPlanCheck, energy_file.encode())
+    if r < 0:
+        raise OptError(txt)
+    return txt if r else ""
+
+
+def schur_pattern(n_eliminated: int, n_retained: int, lists):
+    """Symbolic phase of the explicitly formed Schur complement on the host
+    (OptAMD_SchurPattern). lists: (eliminated vertex per edge, retained vertex per edge) pairs.
+    Returns (counts {instances, pairs, blocks}, rowPtr, colInd, pairPtr, pairs[npairs, 2])."""
+    import numpy as np
+    lib = load_library()
+    ev = [np.ascontiguousarray(a, np.int32) for a, _ in lists]
+    rv = [np.ascontiguousarray(b, np.int32) for _, b in lists]
+    k = len(lists)
+    evp = (_VP * max(k, 1))(*[a.ctypes.data for a in ev])
+    rvp = (_VP * max(k, 1))(*[a.ctypes.data for a in rv])
+    ne = (ctypes.c_longlong * max(k, 1))(*[len(a) for a in ev])
+    counts = (ctypes.c_longlong * 3)()
+    buf = ctypes.create_string_buffer(512)
+    if lib.OptAMD_SchurPattern(n_eliminated, n_retained, k, evp, rvp, ne, counts, None, None, None, None, buf, 512):
+        raise OptError(buf.value.decode())
+    nq, npairs, nnzb = list(counts)
+    row_ptr, col_ind = np.zeros(n_retained + 1, np.int32), np.zeros(nnzb, np.int32)
+    pair_ptr, pairs = np.zeros(nnzb + 1, np.int32), np.zeros((npairs, 2), np.int32)
+    if lib.OptAMD_SchurPattern(n_eliminated, n_retained, k, evp, rvp, ne, counts, row_ptr.ctypes.data, col_ind.ctypes.data,
+                               pair_ptr.ctypes.data, pairs.ctypes.data, buf, 512):
+        raise OptError(buf.value.decode())
+    return {"instances": nq, "pairs": npairs, "blocks": nnzb}, row_ptr, col_ind, pair_ptr, pairs
 
 
 def problem_family(energy_file: str, solver_kind: str = "gaussNewtonGPU") -> str:

@@ -36,6 +36,10 @@ struct GenArgs {
 };
 namespace gen {
 
+// explicit Schur complement: a block of S with more pairs than this is assembled by a whole
+// workgroup (gen_schur_assemble_long; the host lists such blocks), the others by one wave each
+constexpr int kSchurLongPairs = 128;
+
 struct GenSource {
     std::string code;
     bool has_centered = false;   // centred residuals present
@@ -65,6 +69,16 @@ struct GenSource {
     bool graph_apply_centred = false;
     // gen_schur_rhs / gen_schur_elim / gen_schur_apply emitted (Eliminate, codegen_schur.cpp)
     bool has_schur = false;
+    // ReducedSystem("explicit") (codegen_schur_explicit.cpp): gen_schur_eblk, gen_schur_assemble
+    // and gen_schur_spmv emitted. Cr / Ce: channels of the retained / eliminated group, the
+    // retained group's space. Each list is one (eliminated slot, retained slot) pair of one
+    // graph, as GenArgs::slot indices: its instances are the edges in the eliminated slot's
+    // incidence order, and instance q of list l sits at position (sum of the earlier lists'
+    // edge counts) + q of the per-instance buffers.
+    bool has_schur_explicit = false;
+    int schur_cr = 0, schur_ce = 0, schur_rspace = -1;
+    struct SchurList { int graph; int eslot; int rslot; };
+    std::vector<SchurList> schur_lists;
 };
 
 // Generate the kernels for `m` in float (dbl = false) or double. off32: every array a

@@ -228,6 +228,7 @@ void emit_block_pcg(const Ctx& cx, std::ostringstream& o);           // gen_blk_
 // eliminated space); 2: eliminated images read from "w" instead of "p"
 void graph_gather(Ctx& cx, std::ostringstream& o, bool apply, int sp, int schur = 0);
 void emit_schur(Ctx& cx, std::ostringstream& o);                     // gen_schur_rhs, gen_schur_elim, gen_schur_apply
+void emit_schur_explicit(Ctx& cx, std::ostringstream& o);            // gen_schur_eblk, gen_schur_assemble, gen_schur_spmv
 
 }  // namespace gen
 }  // namespace optamd

@@ -985,6 +985,7 @@ private:
     }
     int lp_counter_ = 0;
     int n_eliminate_ = 0;   // Eliminate statements seen
+    int n_reduced_ = 0;     // ReducedSystem statements seen
     void note_index(int idx) { m_->n_params_total = std::max(m_->n_params_total, idx + 1); }
     int channels_of(const Value& t) {
         if (t.k == V::Type) return t.id;
@@ -1277,6 +1278,13 @@ void Interp::install() {
                 err("Eliminate: argument " + std::to_string(i + 1) + " is not an unknown image");
             if (!m_->is_eliminated(a[i].id)) m_->eliminated.push_back(a[i].id);
         }
+        return VList{};
+    });
+    def("ReducedSystem", [this](VList& a) {
+        if (++n_reduced_ > 1) err("a second ReducedSystem (the reduced system has one form)");
+        if (a.size() != 1 || a[0].k != V::Str || (a[0].s != "explicit" && a[0].s != "implicit"))
+            err("ReducedSystem(form): form is \"explicit\" or \"implicit\"");
+        m_->reduced_explicit = a[0].s == "explicit";
         return VList{};
     });
     def("Exclude", [this](VList& a) {
@@ -1694,6 +1702,8 @@ void Interp::finish() {
 // group's space, so that the group's block of J^T J is block-diagonal (one C x C block per
 // element) and the Schur complement on the other spaces needs only per-element inverses.
 void Interp::check_eliminate() {
+    if (n_reduced_ && m_->eliminated.empty())
+        throw LuaError("ReducedSystem: no Eliminate statement (only an energy that eliminates a group has a reduced system)");
     if (m_->eliminated.empty()) return;
     const std::vector<int> unk = m_->unknown_images();
     const int sp = m_->images[m_->eliminated[0]].space;
@@ -1740,6 +1750,53 @@ void Interp::check_eliminate() {
 }
 
 }  // namespace
+
+// ReducedSystem("explicit"): S = B - E M^-1 E^T is assembled from per-instance products, with B
+// taken from the retained group's packed diagonal blocks. That is all of B only when B is
+// block-diagonal, and one block-CSR matrix only when the retained unknowns share one space.
+std::string explicit_refusal(const GModel& m) {
+    if (!m.reduced_explicit || !m.schur()) return "";
+    const std::string head = "ReducedSystem(\"explicit\"): ";
+    auto space_name = [&](int sp) {
+        std::string o = "{";
+        for (size_t k = 0; k < m.spaces[sp].size(); ++k) o += (k ? "," : "") + m.dims[m.spaces[sp][k]].name;
+        return o + "}";
+    };
+    std::vector<int> kept;
+    for (int sp : m.unknown_spaces())
+        if (sp != m.elim_space) kept.push_back(sp);
+    if (kept.size() != 1) {
+        std::string names;
+        for (int sp : kept) names += (names.empty() ? "" : ", ") + space_name(sp);
+        return head + "the retained unknowns lie over " + std::to_string(kept.size()) + " index spaces (" + names +
+               "); the block-sparse S has one block group";
+    }
+    auto offset = [](const Node& n) { return n.off[0] != 0 || n.off[1] != 0 || n.off[2] != 0; };
+    for (auto& c : m.computed)
+        for (auto& g : c.grads) {
+            if (g.u < 0) continue;
+            const Node n = m.pool.at(g.u);
+            if (!m.is_eliminated(n.i) && offset(n))
+                return head + "B is not block-diagonal: ComputedArray '" + m.images[c.image].name + "' depends on " +
+                       m.images[n.i].name + " at an offset";
+        }
+    for (auto& r : m.residuals) {
+        int slot = -1;
+        for (int u : r.unknowns) {
+            const Node n = m.pool.at(u);
+            if (m.is_eliminated(n.i)) continue;
+            if (r.graph < 0 && offset(n))
+                return head + "B is not block-diagonal: a centred residual over " + space_name(kept[0]) + " reads " +
+                       m.images[n.i].name + " at a non-zero offset";
+            if (r.graph >= 0 && slot >= 0 && n.slot != slot)
+                return head + "B is not block-diagonal: a residual of graph '" + m.graphs[r.graph].name + "' reads " +
+                       space_name(kept[0]) + " through two slots ('" + m.graphs[r.graph].slot_names[std::min(slot, n.slot)] +
+                       "', '" + m.graphs[r.graph].slot_names[std::max(slot, n.slot)] + "')";
+            if (r.graph >= 0) slot = n.slot;
+        }
+    }
+    return "";
+}
 
 int GModel::unknown_dims() const {
     for (auto& im : images)

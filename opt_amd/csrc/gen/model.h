@@ -91,6 +91,10 @@ struct GModel {
     // over the other spaces (build_model checks the group, turns the block preconditioner on)
     std::vector<int> eliminated;   // image ids, unknown_images() order
     int elim_space = -1;           // their space, -1 = no Eliminate
+    // ReducedSystem("explicit") beside Eliminate: S is assembled once per step in block-CSR and
+    // PCG's apply is a block SpMV (codegen_schur_explicit.cpp); "implicit" / no statement: the
+    // matrix-free apply. The shapes this form takes: explicit_refusal()
+    bool reduced_explicit = false;
     bool schur() const { return elim_space >= 0; }
     bool is_eliminated(int image) const {
         for (int k : eliminated)
@@ -108,6 +112,10 @@ struct GModel {
     std::vector<int> unknown_images() const;   // image ids of the unknowns, declaration order
     std::vector<GBlockGroup> block_groups() const;       // in unknown_spaces() order
 };
+
+// Why ReducedSystem("explicit") cannot serve this model ("" = it can): the retained unknowns
+// must lie over one index space and B, their block of J^T J, must be block-diagonal (lua.cpp).
+std::string explicit_refusal(const GModel& m);
 
 // Run `text` (an Opt energy file). false + message on a Lua or DSL error.
 bool build_model(const std::string& text, GModel* m, std::string* err);

@@ -20,6 +20,7 @@
 #include <mutex>
 #include "gen/codegen.h"
 #include "graph_util.h"
+#include "schur_pattern.h"
 #include "stencil_plan.h"
 
 namespace optamd {
@@ -199,6 +200,8 @@ bool generic_signature(const std::string& text, std::string* sig, bool* use_pre,
     if (m.block_preconditioner) s += "B;";
     // Eliminate: the group's index space (such a file always runs on generated kernels)
     if (m.schur()) s += "S" + std::to_string(m.elim_space) + ";";
+    // ReducedSystem("explicit"): the reduced system's form ("implicit" is no statement)
+    if (m.schur() && m.reduced_explicit) s += "RX;";
     *sig = s;
     if (use_pre) *use_pre = m.use_preconditioner;
     return true;
@@ -329,6 +332,7 @@ public:
         for (int k = 0; k < 16; ++k) { dfree(goff_[k]); dfree(geid_[k]); }
         for (int k = 0; k < 32; ++k) dfree(gnb_[k]);
         dfree(fp_scratch_);
+        schur_explicit_release();
         if (mod_) (void)hipModuleUnload(mod_);
     }
 
@@ -550,6 +554,95 @@ public:
     void schur_apply(const T* p, T* Ap, const T* dadd, const int* stop, ReduceSlot rs, hipStream_t s) {
         launch(k_schur_apply_, s, {&a_, &p, &w_, &Ap, &dadd, &stop, &rs});
     }
+    // ---- the explicitly formed S (ReducedSystem("explicit"); gen/codegen_schur_explicit.cpp) ----
+    // Symbolic phase (host, schur_pattern.h): block-CSR pattern and per-block pair lists, built
+    // from the vertex arrays at the first use and again when the graphs were re-wired. Numeric
+    // phase, once per Step between schur_rhs (M_e^-1 in blk) and block_init (which inverts B_r
+    // in place): schur_eblk writes W_q, Y_q per edge instance, schur_assemble sums the blocks.
+    // schur_spmv then is gen_schur_apply's contract on the assembled matrix.
+    bool schur_explicit() const { return src_.has_schur_explicit; }
+    bool schur_symbolic_stale() const { return !sx_rowptr_ || sx_generation_ != topology_generation_; }
+    void schur_symbolic(hipStream_t s) {
+        if (!schur_symbolic_stale()) return;
+        schur_explicit_release();   // the old wiring's buffers first: both need not fit together
+        if (src_.schur_lists.size() > 16) throw PlanError("generic: ReducedSystem(\"explicit\"): more than 16 instance lists");
+        std::map<int, std::vector<int>> host;   // GenArgs::slot index -> its vertices
+        std::vector<SchurList> lists;
+        for (auto& l : src_.schur_lists)
+            for (int sb : {l.eslot, l.rslot})
+                if (!host.count(sb)) {
+                    host[sb].resize(std::max(1, nedge_[l.graph]));
+                    OPT_HIP_CHECK(hipMemcpyAsync(host[sb].data(), a_.slot[sb], sizeof(int) * nedge_[l.graph],
+                                                 hipMemcpyDeviceToHost, s));
+                }
+        OPT_HIP_CHECK(hipStreamSynchronize(s));
+        for (auto& l : src_.schur_lists) lists.push_back({host[l.eslot].data(), host[l.rslot].data(), nedge_[l.graph]});
+        SchurPattern P;
+        try {
+            schur_pattern_build(snpix_[m_.elim_space], snpix_[src_.schur_rspace], lists, &P);
+        } catch (const std::length_error& e) {
+            throw PlanError(std::string("generic: ") + e.what());
+        }
+        for (size_t l = 0; l < P.base.size(); ++l) sx_qb_.b[l] = P.base[l];
+        sx_nnzb_ = P.n_blocks();
+        sx_npairs_ = P.n_pairs();
+        sx_nq_ = P.n_instances;
+        auto up = [&](const std::vector<int>& v) {
+            int* d = (int*)dmalloc(sizeof(int) * std::max<size_t>(1, v.size()));
+            if (!v.empty()) OPT_HIP_CHECK(hipMemcpyAsync(d, v.data(), sizeof(int) * v.size(), hipMemcpyHostToDevice, s));
+            return d;
+        };
+        sx_rowptr_ = up(P.rowPtr);
+        sx_colind_ = up(P.colInd);
+        sx_blkrow_ = up(P.blkRow);
+        sx_pairptr_ = up(P.pairPtr);
+        sx_pairs_ = up(P.pairs);
+        std::vector<int> lng;   // blocks gen_schur_assemble leaves to gen_schur_assemble_long
+        for (long long b = 0; b < sx_nnzb_; ++b)
+            if (P.pairPtr[b + 1] - P.pairPtr[b] > gen::kSchurLongPairs) lng.push_back((int)b);
+        sx_nlong_ = (int)lng.size();
+        sx_long_ = up(lng);
+        OPT_HIP_CHECK(hipStreamSynchronize(s));   // (the host vectors go out of scope)
+        const size_t cw = (size_t)src_.schur_cr * src_.schur_ce, cc = (size_t)src_.schur_cr * src_.schur_cr;
+        sx_val_ = (T*)dmalloc(sizeof(T) * std::max<size_t>(1, cc * sx_nnzb_));
+        sx_w_ = (T*)dmalloc(sizeof(T) * std::max<size_t>(1, cw * sx_nq_));
+        sx_y_ = (T*)dmalloc(sizeof(T) * std::max<size_t>(1, cw * sx_nq_));
+        sx_generation_ = topology_generation_;
+    }
+    void schur_eblk(hipStream_t s) { launch(k_schur_eblk_, s, {&a_, &blk_, &sx_w_, &sx_y_, &sx_qb_}); }
+    void schur_assemble(hipStream_t s) {
+        const int nnzb = (int)sx_nnzb_;
+        const int grid = (int)std::max<long long>(1, std::min<long long>((sx_nnzb_ + 3) / 4, 1 << 18));
+        launch_grid(k_schur_assemble_, grid, s, {&a_, &blk_, &sx_w_, &sx_y_, &sx_blkrow_, &sx_colind_, &sx_pairptr_, &sx_pairs_,
+                                                 &sx_val_, &nnzb});
+        if (sx_nlong_ > 0)
+            launch_grid(k_schur_assemble_long_, std::min(sx_nlong_, 1 << 16), s,
+                        {&a_, &blk_, &sx_w_, &sx_y_, &sx_blkrow_, &sx_colind_, &sx_pairptr_, &sx_pairs_, &sx_val_, &sx_long_,
+                         &sx_nlong_});
+    }
+    void schur_spmv(const T* p, T* Ap, const T* dadd, const int* stop, ReduceSlot rs, hipStream_t s) {
+        launch(k_schur_spmv_, s, {&a_, &sx_rowptr_, &sx_colind_, &sx_val_, &p, &Ap, &dadd, &stop, &rs});
+    }
+    // block rows, block dimension, blocks; false before the first symbolic phase
+    bool schur_matrix_shape(long long* rows, int* dim, long long* nnzb) const {
+        if (!src_.has_schur_explicit || !sx_rowptr_) return false;
+        if (rows) *rows = snpix_[src_.schur_rspace];
+        if (dim) *dim = src_.schur_cr;
+        if (nnzb) *nnzb = sx_nnzb_;
+        return true;
+    }
+    long long schur_matrix_pairs() const { return sx_npairs_; }
+    void schur_matrix_copy(int* rowPtr, int* colInd, T* val, hipStream_t s) {
+        const long long nR = snpix_[src_.schur_rspace];
+        OPT_HIP_CHECK(hipMemcpyAsync(rowPtr, sx_rowptr_, sizeof(int) * (nR + 1), hipMemcpyDefault, s));
+        OPT_HIP_CHECK(hipMemcpyAsync(colInd, sx_colind_, sizeof(int) * sx_nnzb_, hipMemcpyDefault, s));
+        OPT_HIP_CHECK(hipMemcpyAsync(val, sx_val_, sizeof(T) * sx_nnzb_ * src_.schur_cr * src_.schur_cr, hipMemcpyDefault, s));
+    }
+    // the buffers the captured PCG loop's SpMV bakes in (StencilPlan::pcg_graph_begin)
+    void schur_explicit_key(std::vector<unsigned long long>* key) const {
+        for (const void* q : {(const void*)sx_rowptr_, (const void*)sx_colind_, (const void*)sx_val_})
+            key->push_back((unsigned long long)(uintptr_t)q);
+    }
     void apply(const T* p, T* Ap, const T* dadd, const int* stop, ReduceSlot rs, hipStream_t s) {
         if (!src_.has_graph) {
             int finish = 1;
@@ -697,6 +790,12 @@ private:
                             std::make_pair(&k_schur_apply_, "gen_schur_apply")})
                 OPT_HIP_CHECK(hipModuleGetFunction(kv.first, mod_, kv.second));
         }
+        if (src_.has_schur_explicit) {
+            for (auto kv : {std::make_pair(&k_schur_eblk_, "gen_schur_eblk"), std::make_pair(&k_schur_assemble_, "gen_schur_assemble"),
+                            std::make_pair(&k_schur_assemble_long_, "gen_schur_assemble_long"),
+                            std::make_pair(&k_schur_spmv_, "gen_schur_spmv")})
+                OPT_HIP_CHECK(hipModuleGetFunction(kv.first, mod_, kv.second));
+        }
         // (the strip J^T F has no block accumulation: block energies keep the gather)
         if (src_.has_jtf_strip && !slab && !m_.block_preconditioner) {
             const char* wj = getenv("OPT_AMD_GEN_JTF");
@@ -721,9 +820,16 @@ private:
             OPT_HIP_CHECK(hipModuleGetFunction(&k_pre_[k], mod_, ("gen_precompute_" + std::to_string(k)).c_str()));
     }
     void launch(hipFunction_t f, hipStream_t s, std::initializer_list<const void*> args) {
+        launch_grid(f, stencil_blocks(), s, args);
+    }
+    void launch_grid(hipFunction_t f, int grid, hipStream_t s, std::initializer_list<const void*> args) {
         std::vector<void*> a;
         for (const void* p : args) a.push_back(const_cast<void*>(p));
-        OPT_HIP_CHECK(hipModuleLaunchKernel(f, stencil_blocks(), 1, 1, kBlock, 1, 1, 0, s, a.data(), nullptr));
+        OPT_HIP_CHECK(hipModuleLaunchKernel(f, grid, 1, 1, kBlock, 1, 1, 0, s, a.data(), nullptr));
+    }
+    void schur_explicit_release() {
+        for (int** q : {&sx_rowptr_, &sx_colind_, &sx_blkrow_, &sx_pairptr_, &sx_pairs_, &sx_long_}) { dfree(*q); *q = nullptr; }
+        for (T** q : {&sx_val_, &sx_w_, &sx_y_}) { dfree(*q); *q = nullptr; }
     }
     // vertex indices must lie in [0, N) (fail-stop, as the reference does on bad input)
     void check_graphs(hipStream_t s) {
@@ -846,6 +952,15 @@ private:
     T* blk_ = nullptr;                       // the plan's block buffer (set_block_buffer)
     hipFunction_t k_schur_rhs_{}, k_schur_elim_{}, k_schur_apply_{};
     T *w_ = nullptr, *be_ = nullptr;         // the plan's compact Schur vectors (set_schur_buffers)
+    // explicit S: kernels, the pattern (block-CSR, block rows, pair lists), values, W_q / Y_q
+    hipFunction_t k_schur_eblk_{}, k_schur_assemble_{}, k_schur_assemble_long_{}, k_schur_spmv_{};
+    int* sx_long_ = nullptr;                 // blocks with more than gen::kSchurLongPairs pairs
+    int sx_nlong_ = 0;
+    struct QBase { long long b[16]; } sx_qb_{};
+    unsigned long long sx_generation_ = 0;   // topology_generation_ the pattern was built for
+    long long sx_nnzb_ = 0, sx_npairs_ = 0, sx_nq_ = 0;
+    int *sx_rowptr_ = nullptr, *sx_colind_ = nullptr, *sx_blkrow_ = nullptr, *sx_pairptr_ = nullptr, *sx_pairs_ = nullptr;
+    T *sx_val_ = nullptr, *sx_w_ = nullptr, *sx_y_ = nullptr;
 };
 
 std::unique_ptr<Plan> make_generic_plan(const ProblemSpec& spec, const StateOptions& opts, const unsigned* dims,
@@ -874,6 +989,10 @@ std::unique_ptr<Plan> make_generic_plan(const ProblemSpec& spec, const StateOpti
         *err = "generic: no materialized Jacobian (useMaterializedJTJ / useFusedJTJ) with Eliminate: the Schur "
                "complement runs matrix-free";
         return nullptr;
+    }
+    {
+        const std::string why = gen::explicit_refusal(m);
+        if (!why.empty()) { *err = "generic: " + why; return nullptr; }
     }
     if (m.multi()) {
         if (opts.materialized || opts.fused_jtj) {
@@ -945,6 +1064,15 @@ int generic_describe(const std::string& text, std::string* out) {
     }
     *out = s;
     return (int)m.residuals.size();
+}
+
+int generic_plan_check(const std::string& text, std::string* why) {
+    gen::GModel m;
+    if (!gen::build_model(text, &m, why)) return -1;
+    const std::string r = gen::explicit_refusal(m);
+    if (r.empty()) return 0;
+    *why = "generic: " + r;
+    return 1;
 }
 
 // Compile check without a device (hiprtc only): 0 ok, else -1 + log.

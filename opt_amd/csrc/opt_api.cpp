@@ -15,6 +15,7 @@
 #include "csr.h"
 #include "plan.h"
 #include "problem.h"
+#include "schur_pattern.h"
 
 static_assert(sizeof(Opt_InitializationParameters) == 44,
               "Opt_InitializationParameters must keep the reference layout (Opt.h:10-35)");
@@ -258,6 +259,17 @@ int OptAMD_ApplyReduced(Opt_State* state, Opt_Plan* plan, void** params, const v
     if (!valid_state(state, "OptAMD_ApplyReduced") || !valid_plan(plan, "OptAMD_ApplyReduced") || !p || !Sp) return 1;
     return guarded(plan, "OptAMD_ApplyReduced", 1, [&] { return plan->impl->apply_reduced(params, p, Sp); });
 }
+int OptAMD_PlanReducedMatrixShape(Opt_Plan* plan, long long* blockRows, int* blockDim, long long* nnzBlocks) {
+    if (!valid_plan(plan, "OptAMD_PlanReducedMatrixShape")) return -1;
+    return plan->impl->reduced_matrix_shape(blockRows, blockDim, nnzBlocks) ? 1 : 0;
+}
+int OptAMD_ReducedMatrix(Opt_Plan* plan, void** params, int* rowPtr, int* colInd, void* val) {
+    if (!valid_plan(plan, "OptAMD_ReducedMatrix")) return 1;
+    const int given = (rowPtr ? 1 : 0) + (colInd ? 1 : 0) + (val ? 1 : 0);
+    if (given != 0 && given != 3) return 1;
+    plan->error.clear();
+    return guarded(plan, "OptAMD_ReducedMatrix", 1, [&] { return plan->impl->reduced_matrix(params, rowPtr, colInd, val); });
+}
 int OptAMD_ApplyJTJ(Opt_State* state, Opt_Plan* plan, void** params, const void* p, void* Ap,
                     double* pAp) {
     if (!valid_state(state, "OptAMD_ApplyJTJ") || !valid_plan(plan, "OptAMD_ApplyJTJ") || !p || !Ap)
@@ -480,6 +492,38 @@ int OptAMD_GenericCompileCheck(const char* filename, int doublePrecision, char* 
     const int r = optamd::generic_compile_check(text, doublePrecision != 0, &log);
     copy_name(log, buf, n);
     return r;
+}
+int OptAMD_GenericPlanCheck(const char* filename, char* buf, int n) {
+    std::string text, why;
+    if (!read_file(filename, &text)) return copy_name("cannot read energy file", buf, n), -1;
+    const int r = optamd::generic_plan_check(text, &why);
+    copy_name(why, buf, n);
+    return r;
+}
+int OptAMD_SchurPattern(long long nEliminated, long long nRetained, int nLists, const int* const* elimVertex,
+                        const int* const* retVertex, const long long* nEdges, long long* counts, int* rowPtr,
+                        int* colInd, int* pairPtr, int* pairs, char* buf, int n) {
+    if (nEliminated < 0 || nRetained < 0 || nLists < 0 || (nLists && (!elimVertex || !retVertex || !nEdges)))
+        return copy_name("invalid arguments", buf, n), -1;
+    std::vector<optamd::SchurList> lists;
+    for (int l = 0; l < nLists; ++l) {
+        for (long long e = 0; e < nEdges[l]; ++e)
+            if (elimVertex[l][e] < 0 || elimVertex[l][e] >= nEliminated || retVertex[l][e] < 0 || retVertex[l][e] >= nRetained)
+                return copy_name("list " + std::to_string(l) + ": vertex index outside its space at edge " + std::to_string(e), buf, n), -1;
+        lists.push_back({elimVertex[l], retVertex[l], nEdges[l]});
+    }
+    optamd::SchurPattern P;
+    try {
+        optamd::schur_pattern_build(nEliminated, nRetained, lists, &P);
+    } catch (const std::exception& e) {
+        return copy_name(e.what(), buf, n), -1;
+    }
+    if (counts) { counts[0] = P.n_instances; counts[1] = P.n_pairs(); counts[2] = P.n_blocks(); }
+    if (rowPtr) std::copy(P.rowPtr.begin(), P.rowPtr.end(), rowPtr);
+    if (colInd) std::copy(P.colInd.begin(), P.colInd.end(), colInd);
+    if (pairPtr) std::copy(P.pairPtr.begin(), P.pairPtr.end(), pairPtr);
+    if (pairs) std::copy(P.pairs.begin(), P.pairs.end(), pairs);
+    return 0;
 }
 int OptAMD_GenericDescribe(const char* filename, char* buf, int n) {
     std::string text, out;

@@ -168,6 +168,18 @@ public:
         (void)params; (void)p; (void)Sp;
         return 1;
     }
+    // The explicitly formed S (ReducedSystem("explicit"), include/opt_amd.h): its block-CSR
+    // shape once the graphs are bound (false before, and on every other plan), and S assembled
+    // at the current unknowns, copied to the caller's arrays (all three null: bind and build
+    // the pattern only). 1 where the plan has no explicit reduced system.
+    virtual bool reduced_matrix_shape(long long* rows, int* dim, long long* nnzb) const {
+        (void)rows; (void)dim; (void)nnzb;
+        return false;
+    }
+    virtual int reduced_matrix(void** params, int* rowPtr, int* colInd, void* val) {
+        (void)params; (void)rowPtr; (void)colInd; (void)val;
+        return 1;
+    }
 
     void set_solver_param(const char* name, const void* value);
     // the device scalar slots (red_.scalars) to the host, up to n; the count copied

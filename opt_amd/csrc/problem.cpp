@@ -272,6 +272,15 @@ struct Parser {
                 for (auto& x : a)
                     if (is_single(x, Tk::Name)) spec->eliminate.push_back(t[x.first].text);
                 spec->use_preconditioner = spec->block_preconditioner = true;
+            } else if (f == "ReducedSystem") {
+                // the form of Eliminate's reduced system; the general front end checks it
+                // (gen/lua.cpp) and the plan the shapes the explicit form takes
+                args(i + 1, &a);
+                if (a.size() != 1 || !is_single(a[0], Tk::String) ||
+                    (t[a[0].first].text != "explicit" && t[a[0].first].text != "implicit"))
+                    return fail(i, "ReducedSystem(form): form is \"explicit\" or \"implicit\"");
+                if (!spec->reduced_system.empty()) return fail(i, "a second ReducedSystem (the reduced system has one form)");
+                spec->reduced_system = t[a[0].first].text;
             } else if (f == "Exclude") {
                 spec->n_exclude++;
             } else if (f == "ComputedArray") {

@@ -42,6 +42,7 @@ struct ProblemSpec {
     bool use_preconditioner = false;  // default: opt.ProblemSpec, API/src/o.t:258
     bool block_preconditioner = false;   // UsePreconditioner("block"): generated kernels only
     std::vector<std::string> eliminate;  // Eliminate(X, ...): the group's unknowns (generated kernels only)
+    std::string reduced_system;          // ReducedSystem(form): "explicit" / "implicit", "" without the statement
     int n_exclude = 0;
     std::vector<std::string> computed_arrays;
     bool uses_sampled_image = false;
@@ -68,6 +69,10 @@ bool generic_accepts(const std::string& text, ProblemSpec* spec, std::string* er
 int generic_source(const std::string& text, bool dbl, std::string* out, bool off32 = false);
 int generic_describe(const std::string& text, std::string* out);
 int generic_compile_check(const std::string& text, bool dbl, std::string* log);
+// The shape checks Opt_ProblemPlan runs on the lowered energy before it asks for a device
+// (ReducedSystem("explicit")'s accepted shapes): 0 accepted, 1 refused + the plan's message,
+// -1 + the front end's message if the energy does not lower.
+int generic_plan_check(const std::string& text, std::string* why);
 // Structural signature of the lowered energy (declarations + residual templates, names
 // dropped); false + message if the front end cannot lower it.
 bool generic_signature(const std::string& text, std::string* sig, bool* use_pre, std::string* err);

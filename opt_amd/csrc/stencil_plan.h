@@ -611,6 +611,8 @@ public:
             key.push_back((unsigned long long)(uintptr_t)z_);
         }
         if (schur_) key.push_back((unsigned long long)(uintptr_t)w_);
+        if constexpr (HasSchur<Op>::value)
+            if (explicit_) op_->schur_explicit_key(&key);
         if constexpr (!HasCaptureKey<Op>::value) {
             for (const DeclImage& im : spec_.images)   // arrays by address, scalars by value (below)
                 if (im.index >= 0 && im.index < spec_.n_params_total)
@@ -775,33 +777,37 @@ public:
         if constexpr (HasSchur<Op>::value) {
             if (!schur_) return 1;
             begin_call();
-            prepare(params);
-            const int use_pre = spec_.use_preconditioner ? 1 : 0;
-            const long long lo = pix_lo(), hi = pix_hi();
-            red_.ensure(std::max(op_->stencil_blocks(), 4096), 4, kScBase + kSlots * (std::max(0, sp_.lIterations) + 2));
-            op_->jtf(r_, diag_, flags_, stream_);
-            if (!lm_) {
-                hipLaunchKernelGGL((gn_init_kernel<T>), dim3(fg()), dim3(kBlock), 0, stream_, L_, (const uint8_t*)flags_,
-                                   r_, (const T*)diag_, pre_, p_, use_pre, lo, hi, red_.slot(fg(), kScTmp));
-            } else {
-                LMScalars lm{initialised_ ? radius_ : sp_.trust_region_radius, sp_.min_lm_diagonal, sp_.max_lm_diagonal};
-                if (!initialised_ || n_iter_ == 0)
-                    hipLaunchKernelGGL((lm_init_kernel<T, true>), dim3(fg()), dim3(kBlock), 0, stream_, L_,
-                                       (const uint8_t*)flags_, r_, (const T*)diag_, SSq_, CtC_, pre_, b_, p_,
-                                       use_pre, lm, lo, hi, red_.slot(fg(), kScTmp));
-                else
-                    hipLaunchKernelGGL((lm_init_kernel<T, false>), dim3(fg()), dim3(kBlock), 0, stream_, L_,
-                                       (const uint8_t*)flags_, r_, (const T*)diag_, SSq_, CtC_, pre_, b_, p_,
-                                       use_pre, lm, lo, hi, red_.slot(fg(), kScTmp));
-            }
-            OPT_HIP_CHECK(hipGetLastError());
-            schur_prepare(false);
+            reduced_prepare(params);
             op_->block_init(r_, pre_, CtC_, z_, p_, lm_ ? 1 : 0, red_.slot(nb(), kScTmp), stream_);
             schur_apply((const T*)pin, (T*)Sp, lm_ ? CtC_ : nullptr, nullptr, red_.slot(nb(), kScTmp));
             end_call();
             return 0;
         }
         return Plan::apply_reduced(params, pin, Sp);
+    }
+    bool reduced_matrix_shape(long long* rows, int* dim, long long* nnzb) const override {
+        if constexpr (HasSchur<Op>::value)
+            if (explicit_) return op_->schur_matrix_shape(rows, dim, nnzb);
+        return Plan::reduced_matrix_shape(rows, dim, nnzb);
+    }
+    // S at the current unknowns: the preparation of apply_reduced (whose schur_prepare runs
+    // the numeric phase), then the block-CSR copied out; every buffer the preparation writes
+    // is rebuilt by the next step
+    int reduced_matrix(void** params, int* rowPtr, int* colInd, void* val) override {
+        if constexpr (HasSchur<Op>::value) {
+            if (!explicit_) return 1;
+            begin_call();
+            if (!rowPtr) {   // bind + pattern only
+                op_->bind(params, stream_);
+                schur_symbolic();
+            } else {
+                reduced_prepare(params);
+                op_->schur_matrix_copy(rowPtr, colInd, (T*)val, stream_);
+            }
+            end_call();
+            return 0;
+        }
+        return Plan::reduced_matrix(params, rowPtr, colInd, val);
     }
     int preconditioner_blocks(int max_images, int* group, int* first_row) const override {
         if constexpr (HasBlockPre<Op>::value)
@@ -934,6 +940,7 @@ private:
                 OPT_HIP_CHECK(hipMemset(w_, 0, sizeof(T) * ne));
                 OPT_HIP_CHECK(hipMemset(be_, 0, sizeof(T) * ne));
                 op_->set_schur_buffers(w_, be_);
+                explicit_ = op_->schur_explicit();
             }
         }
         flags_ = (uint8_t*)dmalloc(dom_.npix_mem());
@@ -957,6 +964,43 @@ private:
         op_.reset();
     }
 
+    // the stand-alone reduced entry points' preparation: bind, J^T F and its blocks, the
+    // scalar init kernel as in step(), then schur_prepare without the right-hand side
+    void reduced_prepare(void** params) {
+        prepare(params);
+        const int use_pre = spec_.use_preconditioner ? 1 : 0;
+        const long long lo = pix_lo(), hi = pix_hi();
+        red_.ensure(std::max(op_->stencil_blocks(), 4096), 4, kScBase + kSlots * (std::max(0, sp_.lIterations) + 2));
+        op_->jtf(r_, diag_, flags_, stream_);
+        if (!lm_) {
+            hipLaunchKernelGGL((gn_init_kernel<T>), dim3(fg()), dim3(kBlock), 0, stream_, L_, (const uint8_t*)flags_,
+                               r_, (const T*)diag_, pre_, p_, use_pre, lo, hi, red_.slot(fg(), kScTmp));
+        } else {
+            LMScalars lm{initialised_ ? radius_ : sp_.trust_region_radius, sp_.min_lm_diagonal, sp_.max_lm_diagonal};
+            if (!initialised_ || n_iter_ == 0)
+                hipLaunchKernelGGL((lm_init_kernel<T, true>), dim3(fg()), dim3(kBlock), 0, stream_, L_,
+                                   (const uint8_t*)flags_, r_, (const T*)diag_, SSq_, CtC_, pre_, b_, p_,
+                                   use_pre, lm, lo, hi, red_.slot(fg(), kScTmp));
+            else
+                hipLaunchKernelGGL((lm_init_kernel<T, false>), dim3(fg()), dim3(kBlock), 0, stream_, L_,
+                                   (const uint8_t*)flags_, r_, (const T*)diag_, SSq_, CtC_, pre_, b_, p_,
+                                   use_pre, lm, lo, hi, red_.slot(fg(), kScTmp));
+        }
+        OPT_HIP_CHECK(hipGetLastError());
+        schur_prepare(false);
+    }
+    // explicit plans: the pattern of S for the graphs as bound (host; a no-op while the wiring
+    // stands). A rebuild moves the SpMV's buffers, so no captured loop survives it.
+    void schur_symbolic() {
+        if constexpr (HasSchur<Op>::value)
+            if (explicit_ && op_->schur_symbolic_stale()) {
+                drop_graph();
+                tbegin("schur_symbolic");
+                op_->schur_symbolic(stream_);
+                tend();
+            }
+    }
+
     // Schur plans, after the scalar init kernel and before block_init: M_e^-1 in place of the
     // eliminated blocks, b_e stashed and cleared, 1/2 b_e.M^-1 b_e beside q0 (gen_blk_step2's exit
     // test adds it); with `rhs` also r_r -= E M^-1 b_e (b_ too in LM) through one reduced apply
@@ -973,10 +1017,21 @@ private:
                     OPT_HIP_CHECK(hipGetLastError());
                 }
                 tend();
+                if (explicit_) {   // S itself: M_e^-1 is in blk, B_r not yet inverted
+                    schur_symbolic();
+                    tbegin("schur_eblk"); op_->schur_eblk(stream_); tend();
+                    tbegin("schur_assemble"); op_->schur_assemble(stream_); tend();
+                }
             }
     }
-    // the reduced apply Ap = S p (two launches); false on a plan without Eliminate
+    // the reduced apply Ap = S p (two launches, or the block SpMV of an explicit plan); false
+    // on a plan without Eliminate
     bool schur_apply(const T* p, T* Ap, const T* dadd, const int* stop, ReduceSlot rs) {
+        if constexpr (HasSchur<Op>::value)
+            if (schur_ && explicit_) {
+                tbegin("schur_spmv"); op_->schur_spmv(p, Ap, dadd, stop, rs, stream_); tend();
+                return true;
+            }
         if constexpr (HasSchur<Op>::value)
             if (schur_) {
                 tbegin("schur_elim"); op_->schur_elim(p, stream_); tend();
@@ -1112,6 +1167,7 @@ private:
     T *blk_ = nullptr, *z_ = nullptr;          // its blocks (inverted in place) and z = M^-1 r
     bool schur_ = false;                       // Eliminate: PCG on the Schur complement (HasSchur)
     T *w_ = nullptr, *be_ = nullptr;           // compact (eliminated elements): M^-1-sized products, the stash of b_e
+    bool explicit_ = false;                    // ReducedSystem("explicit"): S assembled per step, the apply a block SpMV
     uint8_t* flags_ = nullptr;
     int* stop_ = nullptr;
     hipGraphExec_t graph_exec_ = nullptr;      // captured PCG loop (pcg_graph_begin)

@@ -1,16 +1,22 @@
 #!/usr/bin/env python3
-"""Schur-complement PCG (Eliminate(X)) against the scalar and block preconditioners on
+"""Schur-complement PCG (Eliminate(X)), matrix-free and explicitly formed
+(ReducedSystem("explicit")), against the scalar and block preconditioners on
 bundle adjustment at DESIGN §3.6's size: 1 000 cameras, 100 000 points, 1 000 000
 observations (10 distinct random cameras per point), fp32, gaussNewtonGPU.
 
 One process, the variants interleaved (energies/bundle_adjustment.t, its
-UsePreconditioner("block") variant, energies/bundle_adjustment_schur.t; same inputs):
+UsePreconditioner("block") variant, energies/bundle_adjustment_schur.t and
+energies/bundle_adjustment_schur_explicit.t; same inputs):
 
 * the GN step in ms at lIterations = 10 (host clock around a call that ends in a device
   synchronise; median of --reps after a warm-up step);
 * the apply in us per PCG iteration from the plan's per-kernel timer, in a pass of its own:
-  `schur_elim` + `schur_apply` for Schur, `gen_apply` (the timer entry that spans gen_apply
-  and gen_apply_graph) for the others; with them the once-per-step `schur_rhs` / `schur_back`;
+  `schur_elim` + `schur_apply` for Schur, `schur_spmv` for the explicit form, `gen_apply` (the
+  timer entry that spans gen_apply and gen_apply_graph) for the others; with them the
+  once-per-step `schur_rhs` / `schur_back` and the explicit form's `schur_eblk` /
+  `schur_assemble`;
+* explicit: the host symbolic phase in ms (a fresh plan whose incidence lists are built, then
+  the pattern alone), the shape of S, and the SpMV's bytes (blocks x C^2 x 4) over its time;
 * the cost after each of 5 GN steps at lIterations = 10.
 
 --variants picks a subset (a library from before the statement knows no Schur file: run it
@@ -72,7 +78,7 @@ def design_table(paths):
     print("| run | variant | GN step ms | apply us / PCG iteration | cost after GN steps 1..5 |")
     print("|---|---|---|---|---|")
     for p, r in zip(paths, runs):
-        for v in ("scalar", "block", "schur"):
+        for v in ("scalar", "block", "schur", "explicit"):
             if v in r:
                 print("| %s | %s | %.2f | %.0f | %s |" % (os.path.basename(p), v, r[v]["step_ms_median"], r[v]["apply_us_per_iteration"],
                                                       " ".join("%.5g" % c for c in r[v]["cost_after_steps"][1:])))
@@ -86,7 +92,7 @@ def main():
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--reps", type=int, default=7)
-    ap.add_argument("--variants", default="scalar,block,schur")
+    ap.add_argument("--variants", default="scalar,block,schur,explicit")
     ap.add_argument("--out", default="")
     ap.add_argument("--design-table", nargs="+", default=None)
     args = ap.parse_args()
@@ -103,7 +109,8 @@ def main():
     assert "UsePreconditioner(true)" in text
     block = os.path.join(tempfile.mkdtemp(), "bundle_adjustment_block.t")
     open(block, "w").write(text.replace("UsePreconditioner(true)", 'UsePreconditioner("block")'))
-    files = {"scalar": shipped, "block": block, "schur": os.path.join(ROOT, "energies", "bundle_adjustment_schur.t")}
+    files = {"scalar": shipped, "block": block, "schur": os.path.join(ROOT, "energies", "bundle_adjustment_schur.t"),
+             "explicit": os.path.join(ROOT, "energies", "bundle_adjustment_schur_explicit.t")}
     names = [v for v in args.variants.split(",") if v]
 
     dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
@@ -145,14 +152,39 @@ def main():
             one_step(s)
         table = {}
         for n in ("jtf", "gn_init", "blk_init", "step2", "blk_step2", "step3", "gen_apply", "schur_rhs", "schur_elim",
-                  "schur_apply", "schur_back", "update", "cost"):
+                  "schur_apply", "schur_back", "schur_eblk", "schur_assemble", "schur_spmv", "update", "cost"):
             cnt, ms = s.kernel_stat(n)
             if cnt:
                 table[n] = {"launches": cnt, "us_per_launch": 1e3 * ms / cnt}
         s.set_kernel_timing(0)
         us = lambda n: table.get(n, {}).get("us_per_launch", 0.0)
         out[k]["kernels"] = table
-        out[k]["apply_us_per_iteration"] = us("schur_elim") + us("schur_apply") if k == "schur" else us("gen_apply")
+        out[k]["apply_us_per_iteration"] = (us("schur_elim") + us("schur_apply") if k == "schur" else
+                                            us("schur_spmv") if k == "explicit" else us("gen_apply"))
+    if "explicit" in solvers:
+        # the symbolic phase alone: a fresh plan, its incidence lists built by a cost evaluation
+        # first, then the bind-and-pattern call (OptAMD_ReducedMatrix without arrays)
+        from opt_amd.api import ParamPack
+        s2 = OptSolver([w["NC"], w["NP"], w["NO"]], files["explicit"], "gaussNewtonGPU")
+        prm = fresh()
+        s2.eval_cost(prm)
+        pk = ParamPack(prm)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        rc = s2.lib.OptAMD_ReducedMatrix(s2.plan, pk.ptr, None, None, None)
+        ms = (time.perf_counter() - t0) * 1e3
+        assert rc == 0
+        rows, dim, nnzb = s2.reduced_matrix_shape()
+        e = out["explicit"]
+        e["symbolic_build_ms"] = ms
+        e["block_rows"], e["block_dim"], e["blocks"] = rows, dim, nnzb
+        e["spmv_bytes"] = nnzb * dim * dim * 4
+        spmv = e["kernels"].get("schur_spmv", {}).get("us_per_launch", 0.0)
+        e["spmv_TB_per_s"] = e["spmv_bytes"] / (spmv * 1e-6) / 1e12 if spmv else 0.0
+        e["spmv_over_copy_rate"] = e["spmv_TB_per_s"] / 6.29   # the float4 copy rate measured on this chip
+        s2.close()
+    if "schur" in out and "explicit" in out:
+        out["explicit_apply_over_schur_apply"] = out["explicit"]["apply_us_per_iteration"] / out["schur"]["apply_us_per_iteration"]
     if "schur" in out and "scalar" in out:
         out["schur_apply_over_full_apply"] = out["schur"]["apply_us_per_iteration"] / out["scalar"]["apply_us_per_iteration"]
     print(json.dumps(out))
