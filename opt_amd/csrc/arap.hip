@@ -920,6 +920,10 @@ private:
     int *dv0_ = nullptr, *dv1_ = nullptr;
 };
 
+static_assert(HasFusedStep3<ArapOp<float>>::value);   // the optional driver features this Op claims (stencil_plan.h)
+static_assert(HasTopologyGeneration<ArapOp<float>>::value);
+static_assert(HasDumpJ<ArapOp<float>>::value);
+
 std::unique_ptr<Plan> make_arap_plan(const ProblemSpec& spec, const StateOptions& opts, const unsigned* dims,
                                      std::string* err) {
     if (spec.graphs.size() != 1 || spec.graphs[0].vertices.size() != 2 || spec.graphs[0].dims.empty()) {

@@ -963,6 +963,14 @@ private:
     T *sx_val_ = nullptr, *sx_w_ = nullptr, *sx_y_ = nullptr;
 };
 
+static_assert(HasBlockPre<GenericOp<float>>::value);   // the optional driver features this Op claims (stencil_plan.h)
+static_assert(HasSchur<GenericOp<float>>::value);
+static_assert(HasCaptureKey<GenericOp<float>>::value);
+static_assert(HasRefreshCaches<GenericOp<float>>::value);
+static_assert(HasSlabRefusal<GenericOp<float>>::value);
+static_assert(HasTopologyGeneration<GenericOp<float>>::value);
+static_assert(HasDumpJ<GenericOp<float>>::value);
+
 std::unique_ptr<Plan> make_generic_plan(const ProblemSpec& spec, const StateOptions& opts, const unsigned* dims,
                                         std::string* err) {
     ProblemSpec s = spec;

@@ -3242,6 +3242,8 @@ private:
     float *dU_ = nullptr, *dC_ = nullptr, *dM_ = nullptr;
 };
 
+static_assert(HasDumpJ<ImageWarpingOp<float>>::value);   // the optional driver features this Op claims (stencil_plan.h)
+
 std::unique_ptr<Plan> make_image_warping_plan(const ProblemSpec& spec, const StateOptions& opts,
                                               const unsigned* dims, std::string* err) {
     // Dim("W",0), Dim("H",1)

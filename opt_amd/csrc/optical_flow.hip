@@ -470,6 +470,8 @@ private:
     float *dI_ = nullptr, *dIh_ = nullptr, *dIhx_ = nullptr, *dIhy_ = nullptr;
 };
 
+static_assert(HasDumpJ<OpticalFlowOp<float>>::value);   // the optional driver features this Op claims (stencil_plan.h)
+
 std::unique_ptr<Plan> make_optical_flow_plan(const ProblemSpec& spec, const StateOptions& opts,
                                              const unsigned* dims, std::string* err) {
     unsigned W = 0, H = 0;

@@ -302,6 +302,8 @@ private:
     float *dT_ = nullptr, *dM_ = nullptr;
 };
 
+static_assert(HasDumpJ<PoissonOp<float>>::value);   // the optional driver features this Op claims (stencil_plan.h)
+
 std::unique_ptr<Plan> make_poisson_plan(const ProblemSpec& spec, const StateOptions& opts, const unsigned* dims,
                                         std::string* err) {
     unsigned W = 0, H = 0;

@@ -1100,6 +1100,10 @@ private:
     uint8_t *dmR_ = nullptr, *dmC_ = nullptr;
 };
 
+static_assert(HasApplySums<ShapeFromShadingOp<float>>::value);   // the optional driver features this Op claims (stencil_plan.h)
+static_assert(HasApplySplit<ShapeFromShadingOp<float>>::value);
+static_assert(HasApplyExt<ShapeFromShadingOp<float>>::value);
+
 std::unique_ptr<Plan> make_sfs_plan(const ProblemSpec& spec, const StateOptions& opts, const unsigned* dims,
                                     std::string* err) {
     unsigned W = 0, H = 0;

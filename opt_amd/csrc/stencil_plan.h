@@ -82,11 +82,32 @@ __global__ __launch_bounds__(kBlock) void revert_images_kernel(VecLayout L, cons
 //                     — Ap = J^T J p (+ dadd p), sum p.Ap; returns early if *stop
 //   void cost(ReduceSlot, hipStream_t); void model_cost(const T* delta, ReduceSlot, hipStream_t)
 //   void unbind(hipStream_t)                               — copy unknowns back (host mode)
-//   optional, for the materialized path (useMaterializedJTJ, csr.h):
-//   long long jacobian_rows() const, jacobian_nnz() const;
-//   void dump_j(int* rowPtr, int* colInd, T* val, hipStream_t)  — J in CSR (saveJToCRS)
 // All stencil kernels cover the owned rows [y_lo, y_hi) of the Domain and read up to
 // halo() rows beyond them.
+//
+// Optional methods, each with the trait that finds it and the methods that come with it
+// (described at the traits below):
+//   HasDumpJ               dump_j(rowPtr, colInd, val, s); jacobian_rows(), jacobian_nnz()
+//   HasApplySplit          can_split(); apply_split(part, ...apply's arguments)
+//   HasApplySums           apply_sums(part, p, Ap, dadd, stop, rs, r, w, s, e0, e1)
+//   HasFusedStep3          step3_fused(pre, r, p, sc, i_num, i_den, use_pre, stop, s);
+//                          apply_prepared(...apply's arguments)
+//   HasApplyExt            apply_ext(...apply's arguments, e0, e1)
+//   HasSlabRefusal         slab_refusal()
+//   HasRefreshCaches       refresh_caches(s)
+//   HasTopologyGeneration  topology_generation()
+//   HasCaptureKey          capture_key(key)
+//   HasBlockPre            block_pre(); block_entries(), set_block_buffer, block_layout,
+//                          block_init, block_step2, block_half2, block_apply
+//   HasSchur               schur(); schur_entries(), set_schur_buffers, eliminated, schur_rhs,
+//                          schur_elim, schur_apply, schur_back, and for ReducedSystem("explicit")
+//                          schur_explicit(), schur_symbolic_stale, schur_symbolic, schur_eblk,
+//                          schur_assemble, schur_spmv, schur_matrix_shape, schur_matrix_copy,
+//                          schur_explicit_key
+// A trait looks for its first method by NAME only (none of these is overloaded or a
+// template): an Op whose signature drifts fails to compile where the driver calls it,
+// instead of losing the feature without a word. Each Op's source asserts the traits it
+// claims.
 //
 // Row-slab decomposition: each rank owns rows [y_lo, y_hi) and holds
 // halo() rows of each neighbour. The flat PCG kernels run over the whole memory slab:
@@ -95,60 +116,43 @@ __global__ __launch_bounds__(kBlock) void revert_images_kernel(VecLayout L, cons
 // exchanges are: unknowns after bind / update / revert, computed arrays after each
 // precompute, flags after J^T F, p before each apply (delta before an apply of delta
 // and before the model cost); every scalar is all-reduced right after its kernel.
-template <class Op, class = void>
-struct HasDumpJ : std::false_type {};
-template <class Op>
-struct HasDumpJ<Op, std::void_t<decltype(std::declval<Op&>().dump_j((int*)nullptr, (int*)nullptr,
-                                                                     (typename Op::T*)nullptr, hipStream_t{}))>>
-    : std::true_type {};
+#define OPTAMD_OP_TRAIT(Trait, method)                                                          \
+    template <class Op, class = void>                                                           \
+    struct Trait : std::false_type {};                                                          \
+    template <class Op>                                                                         \
+    struct Trait<Op, std::void_t<decltype(&Op::method)>> : std::true_type {}
+
+// The materialized path (useMaterializedJTJ, csr.h): long long jacobian_rows() const,
+// jacobian_nnz() const; void dump_j(int* rowPtr, int* colInd, T* val, hipStream_t) — J in
+// CSR (saveJToCRS).
+OPTAMD_OP_TRAIT(HasDumpJ, dump_j);
 
 // Ops whose apply can run as interior + boundary launches (row slabs: the halo refresh
 // of p overlaps the interior part): bool can_split() const; void apply_split(int part,
 // ... apply's arguments) with part 1 = no halo reads, 2 = the rest, 0 = everything.
-template <class Op, class = void>
-struct HasApplySplit : std::false_type {};
-template <class Op>
-struct HasApplySplit<Op, std::void_t<decltype(std::declval<const Op&>().can_split())>> : std::true_type {};
+OPTAMD_OP_TRAIT(HasApplySplit, can_split);
 
 // Ops whose apply can also reduce the fused PCG step's sums (shape_from_shading):
 // apply_sums(part, p, Ap, dadd, stop, rs, r, w, stream, e0, e1) reduces {p.Ap, r.W Ap,
 // Ap.W Ap, r.W r} (fp64) into rs; the driver then runs PCGStep2 + PCGStep3 as ONE pass
 // (step23_kernel, beta's numerator from the identity over those sums) and, on row slabs,
 // one all-reduce per PCG iteration.
-template <class Op, class = void>
-struct HasApplySums : std::false_type {};
-template <class Op>
-struct HasApplySums<Op, std::void_t<decltype(std::declval<Op&>().apply_sums(
-                            0, (const typename Op::T*)nullptr, (typename Op::T*)nullptr, (const typename Op::T*)nullptr,
-                            (const int*)nullptr, ReduceSlot{}, (const typename Op::T*)nullptr,
-                            (const typename Op::T*)nullptr, hipStream_t{}, hipEvent_t{}, hipEvent_t{}))>>
-    : std::true_type {};
+OPTAMD_OP_TRAIT(HasApplySums, apply_sums);
 
 // Ops that fold PCGStep3 into the first pass of their next apply (ARAP: p = z + beta p
 // per vertex, then K of the new p): step3_fused(pre, r, p, sc, i_num, i_den, use_pre,
 // stop, s) replaces step3_kernel; apply_prepared(...apply's arguments) is the apply
 // without that first pass.
-template <class Op, class = void>
-struct HasFusedStep3 : std::false_type {};
-template <class Op>
-struct HasFusedStep3<Op, std::void_t<decltype(std::declval<Op&>().step3_fused(
-                             (const typename Op::T*)nullptr, (const typename Op::T*)nullptr, (typename Op::T*)nullptr,
-                             (const double*)nullptr, 0, 0, 0, (const int*)nullptr, hipStream_t{}))>> : std::true_type {};
+OPTAMD_OP_TRAIT(HasFusedStep3, step3_fused);
 
 // Optional Op::apply_ext(p, Ap, dadd, stop, rs, stream, e0, e1): the apply with HIP
 // events attached to its launch (hipExtLaunchKernelGGL), so the per-kernel timer measures
 // the kernel itself instead of event records around the launch.
-template <class Op, class = void>
-struct HasApplyExt : std::false_type {};
-template <class Op>
-struct HasApplyExt<Op, std::void_t<decltype(std::declval<Op&>().apply_ext(
-                           (const typename Op::T*)nullptr, (typename Op::T*)nullptr, (const typename Op::T*)nullptr,
-                           (const int*)nullptr, ReduceSlot{}, hipStream_t{}, hipEvent_t{}, hipEvent_t{}))>> : std::true_type {};
+OPTAMD_OP_TRAIT(HasApplyExt, apply_ext);
 
-template <class Op, class = void>
-struct HasSlabRefusal : std::false_type {};
-template <class Op>
-struct HasSlabRefusal<Op, std::void_t<decltype(std::declval<const Op&>().slab_refusal())>> : std::true_type {};
+// Ops that decide per energy whether row slabs are possible: std::string slab_refusal()
+// const, the reason or "".
+OPTAMD_OP_TRAIT(HasSlabRefusal, slab_refusal);
 
 // Ops that keep private per-step caches of values derived from the bound arrays
 // (GenericOp: transcendentals of centred and graph-slot reads, and the sample caches —
@@ -160,11 +164,7 @@ struct HasSlabRefusal<Op, std::void_t<decltype(std::declval<const Op&>().slab_re
 // are rebuilt after each update and revert as well (they ride with precompute). The
 // energy's ComputedArrays themselves keep the reference's schedule (init, after update,
 // after revert) and are NOT refreshed at Step start.
-template <class Op, class = void>
-struct HasRefreshCaches : std::false_type {};
-template <class Op>
-struct HasRefreshCaches<Op, std::void_t<decltype(std::declval<Op&>().refresh_caches(hipStream_t{}))>>
-    : std::true_type {};
+OPTAMD_OP_TRAIT(HasRefreshCaches, refresh_caches);
 
 // Ops whose Jacobian's column structure comes from bound vertex arrays (ArapOp, GenericOp
 // with graphs): topology_generation() is a counter the Op bumps whenever bind finds the
@@ -174,42 +174,29 @@ struct HasRefreshCaches<Op, std::void_t<decltype(std::declval<Op&>().refresh_cac
 // again at the first Step or apply after it moved (materialize below): the Step-boundary
 // contract lets a caller rewrite or rebind the vertex arrays between Steps. Image families
 // have no such method and build their patterns once per plan.
-template <class Op, class = void>
-struct HasTopologyGeneration : std::false_type {};
-template <class Op>
-struct HasTopologyGeneration<Op, std::void_t<decltype(std::declval<const Op&>().topology_generation())>>
-    : std::true_type {};
+OPTAMD_OP_TRAIT(HasTopologyGeneration, topology_generation);
 
 // Ops that describe their own hipGraph capture gate and key (GenericOp: the kernel
 // argument block the generated launches receive) instead of the declaration parser's.
-template <class Op, class = void>
-struct HasCaptureKey : std::false_type {};
-template <class Op>
-struct HasCaptureKey<Op, std::void_t<decltype(std::declval<const Op&>().capture_key(
-                             (std::vector<unsigned long long>*)nullptr))>> : std::true_type {};
+OPTAMD_OP_TRAIT(HasCaptureKey, capture_key);
 
 // Ops with a block preconditioner (GenericOp for UsePreconditioner("block")): block_pre()
 // says whether this energy asked for it; then jtf also fills the plan's block buffer
 // (set_block_buffer, block_entries() values) and block_init / block_step2 / block_half2 /
 // block_apply are the per-element PCG kernels that replace the scalar z = pre r: z goes to
 // its own vector, and PCGStep3 runs on it with use_pre = 0.
-template <class Op, class = void>
-struct HasBlockPre : std::false_type {};
-template <class Op>
-struct HasBlockPre<Op, std::void_t<decltype(std::declval<const Op&>().block_pre())>> : std::true_type {};
+OPTAMD_OP_TRAIT(HasBlockPre, block_pre);
 
 // Ops that can eliminate one group of unknowns (GenericOp for Eliminate(X, ...)): schur()
 // says whether this energy asked for it (then block_pre() holds too). PCG then runs on the
 // Schur complement S = B - E M^-1 E^T over the retained unknowns, in the full vector layout
-// with the eliminated entries of p, r, z, Ap and delta exactly zero: pcg_loop's block path as
-// it is, with the apply replaced by schur_elim (w = -M^-1 E^T p) + schur_apply (B p + E w);
-// before the loop schur_rhs (M_e^-1, the stash of b_e, w = M^-1 b_e) and one schur_apply of
-// p = 0 give the reduced right-hand side b_r - E M^-1 b_e; after it schur_back writes
+// with the eliminated entries of p, r, z, Ap and delta exactly zero: pcg_loop's block stages
+// as they are, with the apply replaced by schur_elim (w = -M^-1 E^T p) + schur_apply (B p +
+// E w); before the loop schur_rhs (M_e^-1, the stash of b_e, w = M^-1 b_e) and one schur_apply
+// of p = 0 give the reduced right-hand side b_r - E M^-1 b_e; after it schur_back writes
 // delta_e = M^-1 (b_e - E^T delta_r), and the update, model cost and cost see the full delta.
-template <class Op, class = void>
-struct HasSchur : std::false_type {};
-template <class Op>
-struct HasSchur<Op, std::void_t<decltype(std::declval<const Op&>().schur())>> : std::true_type {};
+OPTAMD_OP_TRAIT(HasSchur, schur);
+#undef OPTAMD_OP_TRAIT
 
 // r -= Ap (and b = r, LM): the reduced right-hand side from Ap = E M^-1 b_e
 template <typename T>
@@ -315,31 +302,8 @@ public:
         red_.ensure(std::max(op_->stencil_blocks(), 4096), 4, kScBase + kSlots * (Lit + 2));
         OPT_HIP_CHECK(hipMemsetAsync(stop_, 0, 64, stream_));
         OPT_HIP_CHECK(hipMemsetAsync(delta_, 0, sizeof(T) * n_, stream_));   // PCGInit1: delta = 0
-        const int use_pre = spec_.use_preconditioner ? 1 : 0;
-        const long long lo = pix_lo(), hi = pix_hi();
-        // PCGInit1 (+ LM diagonal)
-        tbegin("jtf"); op_->jtf(r_, diag_, flags_, stream_); tend();
-        exchange({{(void*)flags_, (size_t)dom_.W}});
-        if (!lm_) {
-            tbegin("gn_init");
-            hipLaunchKernelGGL((gn_init_kernel<T>), dim3(fg()), dim3(kBlock), 0, stream_, L_, (const uint8_t*)flags_,
-                               r_, (const T*)diag_, pre_, p_, use_pre, lo, hi, red_.slot(fg(), rz(0)));
-            tend();
-        } else {
-            LMScalars lm{radius_, sp_.min_lm_diagonal, sp_.max_lm_diagonal};
-            tbegin("lm_init");
-            if (n_iter_ == 0)
-                hipLaunchKernelGGL((lm_init_kernel<T, true>), dim3(fg()), dim3(kBlock), 0, stream_, L_,
-                                   (const uint8_t*)flags_, r_, (const T*)diag_, SSq_, CtC_, pre_, b_, p_,
-                                   use_pre, lm, lo, hi, red_.slot(fg(), rz(0)));
-            else
-                hipLaunchKernelGGL((lm_init_kernel<T, false>), dim3(fg()), dim3(kBlock), 0, stream_, L_,
-                                   (const uint8_t*)flags_, r_, (const T*)diag_, SSq_, CtC_, pre_, b_, p_,
-                                   use_pre, lm, lo, hi, red_.slot(fg(), rz(0)));
-            tend();
-            OPT_HIP_CHECK(hipMemsetAsync(red_.scalars + kScQ0, 0, sizeof(double), stream_));
-        }
-        OPT_HIP_CHECK(hipGetLastError());
+        linear_init(rz(0), true);   // PCGInit1 (+ LM diagonal)
+        if (lm_) OPT_HIP_CHECK(hipMemsetAsync(red_.scalars + kScQ0, 0, sizeof(double), stream_));
         schur_prepare(true);   // (delta_ = 0 here: the p of the reduced right-hand side's apply)
         if constexpr (HasBlockPre<Op>::value)
             if (block_) {   // M_e^-1 in place of the blocks, z_0 = M^-1 r, p_0 = z_0, rz_0
@@ -351,7 +315,7 @@ public:
         const int* stop = lm_ ? stop_ : nullptr;
         if (mat_) materialize();   // cusparseOuter (:2068): J, J^T (, J^T J) at the current X
         if (pcg_graph_begin(params, Lit)) {
-            pcg_loop(Lit, use_pre, stop);
+            pcg_loop(Lit, stop);
             pcg_graph_end();
         }
         if constexpr (HasSchur<Op>::value)
@@ -375,132 +339,30 @@ public:
         return lm_finish_step();
     }
 
-    // PCG inner loop (PCGStep1-3, :607-845) of one step; launches only, no host sync.
-    void pcg_loop(int Lit, int use_pre, const int* stop) {
+    // PCG inner loop (PCGStep1-3, :607-845) of one step; launches only, no host sync. One
+    // iteration is the stages below (the private pcg_* members, each picks its variant), with
+    // a row-slab run's all-reduces between them.
+    void pcg_loop(int Lit, const int* stop) {
         if constexpr (HasApplySums<Op>::value)
             if (!mat_ && (fuse23_ == 1 || (fuse23_ == 2 && distributed()))) {
-                pcg_loop_fused(Lit, use_pre, stop);
+                pcg_loop_fused(Lit, stop);
                 return;
             }
-        const bool fuse3 = !distributed() && !mat_ && fuse3_on_;
-        // GN with step3_kernel: the delta update rides in PCGStep3 (reads p_old anyway)
-        bool d3 = !lm_ && delta3_on_;
-        if constexpr (HasFusedStep3<Op>::value) d3 = d3 && !fuse3;
         for (int i = 0; i < Lit; ++i) {
             // the zeta test rides in the kernel that reduces q (one GPU), else its own launch
-            const ZetaArgs z{red_.scalars + kScQ0, stop_, i, sp_.q_tolerance, (lm_ && !distributed()) ? 1 : 0};
-            bool split = false;
-            if constexpr (HasApplySplit<Op>::value)
-                split = distributed() && overlap_ && comm_->concurrent_halo() && !mat_ && op_->can_split();
-            if (!split) exchange_vec(p_);
-            if (split) {
-                if constexpr (HasApplySplit<Op>::value) {
-                    // halo refresh of p beside the interior blocks (Plan::halo_mark/begin/join)
-                    tbegin(Op::kApplyName);
-                    halo_mark();
-                    const ReduceSlot rs = red_.slot(nb(), pap(i));
-                    op_->apply_split(1, p_, Ap_, lm_ ? CtC_ : nullptr, stop, rs, stream_);
-                    halo_begin(comm_, vec_planes(p_), dom_, op_->halo());
-                    halo_join();
-                    op_->apply_split(2, p_, Ap_, lm_ ? CtC_ : nullptr, stop, rs, stream_);
-                    tend();
-                }
-            } else if (mat_) {
-                // cusparseInner + PCGStep1_Finish (:2101-2118): the SpMV replaces PCGStep1;
-                // as in the reference, the LM CtC term is not part of this product
-                mat_apply(p_, Ap_, stop, pap(i));
-            } else {
-                bool done = false;
-                if constexpr (HasFusedStep3<Op>::value)
-                    if (i > 0 && fuse3) {   // step3 of i-1 already ran the apply's first pass
-                        tbegin(Op::kApplyName);
-                        op_->apply_prepared(p_, Ap_, lm_ ? CtC_ : nullptr, stop, red_.slot(nb(), pap(i)), stream_);
-                        tend();
-                        done = true;
-                    }
-                if constexpr (HasApplyExt<Op>::value) {
-                    hipEvent_t e0 = nullptr, e1 = nullptr;
-                    if (!done && timer_.mode && timer_.ext_pair(Op::kApplyName, &e0, &e1)) {
-                        op_->apply_ext(p_, Ap_, lm_ ? CtC_ : nullptr, stop, red_.slot(nb(), pap(i)), stream_, e0, e1);
-                        timer_.ext_record(Op::kApplyName, e0, e1);
-                        done = true;
-                    }
-                }
-                if (!done && !schur_apply(p_, Ap_, lm_ ? CtC_ : nullptr, stop, red_.slot(nb(), pap(i)))) {
-                    tbegin(Op::kApplyName);
-                    op_->apply(p_, Ap_, lm_ ? CtC_ : nullptr, stop, red_.slot(nb(), pap(i)), stream_);
-                    tend();
-                }
-            }
+            const ZetaArgs z = zeta_args(i);
+            pcg_apply(i, stop);
             allreduce(pap(i), 1);
-            const bool reset = lm_ && ((i + 1) % std::max(1, sp_.residual_reset_period)) == 0;
-            if (reset) {   // the classic halves, the reference's unguarded division (:742)
-                hipLaunchKernelGGL((half1_kernel<T>), dim3(fg()), dim3(kBlock), 0, stream_, n_, (const T*)p_,
-                                   delta_, red_.scalars, rz(i), pap(i), stop);
-                exchange_vec(delta_);
-                if (!schur_apply(delta_, Adelta_, CtC_, stop, red_.slot(nb(), kScTmp)))
-                    op_->apply(delta_, Adelta_, CtC_, stop, red_.slot(nb(), kScTmp), stream_);
-                bool blk = false;
-                if constexpr (HasBlockPre<Op>::value)
-                    if (block_) {
-                        tbegin("blk_half2");
-                        op_->block_half2(Adelta_, b_, delta_, r_, z_, stop, red_.slot(nb(), rz(i + 1)), z, stream_);
-                        tend();
-                        blk = true;
-                    }
-                if (!blk)
-                hipLaunchKernelGGL((half2_kernel<T>), dim3(fg()), dim3(kBlock), 0, stream_, n_, (const T*)Adelta_,
-                                   (const T*)b_, (const T*)pre_, (const T*)delta_, r_, use_pre, stop,
-                                   red_.slot(fg(), rz(i + 1)), z);
+            if (reset_iteration(i)) {   // the classic halves, the reference's unguarded division (:742)
+                pcg_half1<false>(i, stop);
+                pcg_reset_apply(stop);
+                pcg_half2(i, stop, z);
             } else {
-                bool blk = false;
-                if constexpr (HasBlockPre<Op>::value)
-                    if (block_) {
-                        tbegin("blk_step2");
-                        op_->block_step2(p_, Ap_, b_, r_, delta_, z_, red_.scalars, rz(i), pap(i), i == 0 ? 1 : 0,
-                                         lm_ ? 1 : 0, (lm_ || !d3) ? 1 : 0, stop, red_.slot(nb(), rz(i + 1)), z, stream_);
-                        tend();
-                        blk = true;
-                    }
-                if (!blk) {
-                tbegin("step2");
-                launch_step2(i == 0, rz(i), pap(i), rz(i + 1), stop, z, !d3);
-                tend();
-                }
+                pcg_step2(i, stop, z);
             }
             allreduce(rz(i + 1), lm_ ? 2 : 1);   // rz and q sit side by side
-            tbegin("step3");
-            bool fused = false;
-            if (block_) {   // p = z + beta p on the block path's z (step3_kernel's r), no pre
-                if (d3 && i == 0)
-                    hipLaunchKernelGGL((step3_kernel<T, 1>), dim3(fg()), dim3(kBlock), 0, stream_, n_, (const T*)pre_,
-                                       (const T*)z_, p_, red_.scalars, rz(i + 1), rz(i), 0, stop, delta_, rz(i), pap(i));
-                else if (d3)
-                    hipLaunchKernelGGL((step3_kernel<T, 2>), dim3(fg()), dim3(kBlock), 0, stream_, n_, (const T*)pre_,
-                                       (const T*)z_, p_, red_.scalars, rz(i + 1), rz(i), 0, stop, delta_, rz(i), pap(i));
-                else
-                    hipLaunchKernelGGL((step3_kernel<T>), dim3(fg()), dim3(kBlock), 0, stream_, n_, (const T*)pre_,
-                                       (const T*)z_, p_, red_.scalars, rz(i + 1), rz(i), 0, stop);
-                fused = true;
-            }
-            if constexpr (HasFusedStep3<Op>::value)
-                if (fuse3) {
-                    op_->step3_fused(pre_, r_, p_, red_.scalars, rz(i + 1), rz(i), use_pre, stop, stream_);
-                    fused = true;
-                }
-            if (!fused && d3 && i == 0)
-                hipLaunchKernelGGL((step3_kernel<T, 1>), dim3(fg()), dim3(kBlock), 0, stream_, n_, (const T*)pre_,
-                                   (const T*)r_, p_, red_.scalars, rz(i + 1), rz(i), use_pre, stop, delta_, rz(i), pap(i));
-            else if (!fused && d3)
-                hipLaunchKernelGGL((step3_kernel<T, 2>), dim3(fg()), dim3(kBlock), 0, stream_, n_, (const T*)pre_,
-                                   (const T*)r_, p_, red_.scalars, rz(i + 1), rz(i), use_pre, stop, delta_, rz(i), pap(i));
-            else if (!fused)
-                hipLaunchKernelGGL((step3_kernel<T>), dim3(fg()), dim3(kBlock), 0, stream_, n_, (const T*)pre_,
-                                   (const T*)r_, p_, red_.scalars, rz(i + 1), rz(i), use_pre, stop);
-            tend();
-            if (lm_ && !z.on)
-                hipLaunchKernelGGL((zeta_kernel<T>), dim3(1), dim3(1), 0, stream_, red_.scalars, q(i + 1),
-                                   red_.scalars + kScQ0, i, sp_.q_tolerance, stop_);
+            if (!pcg_step3_fused(i, stop)) pcg_step3<false>(i, stop);
+            if (lm_ && !z.on) pcg_zeta(i);
             OPT_HIP_CHECK(hipGetLastError());
         }
     }
@@ -511,73 +373,27 @@ public:
     // zeta test on the all-reduced q before the next step23 (the apply in between is
     // wasted when it stops: the reference would have left the loop before it). Residual-reset
     // iterations (LM) run the classic sequence.
-    void pcg_loop_fused(int Lit, int use_pre, const int* stop) {
-        const T* w = use_pre ? pre_ : nullptr;   // PCGStep2's weighting W (1 without a preconditioner)
+    void pcg_loop_fused(int Lit, const int* stop) {
         bool pending = false;   // rz(i) / q(i) of the previous step23 not all-reduced yet
         for (int i = 0; i < Lit; ++i) {
-            const ZetaArgs z{red_.scalars + kScQ0, stop_, i, sp_.q_tolerance, (lm_ && !distributed()) ? 1 : 0};
-            bool split = false;
-            if constexpr (HasApplySplit<Op>::value)
-                split = distributed() && overlap_ && comm_->concurrent_halo() && op_->can_split();
-            const ReduceSlot rs = red_.slot(nb(), pap(i));
-            auto launch = [&](int part) {
-                hipEvent_t e0 = nullptr, e1 = nullptr;
-                const bool ev = part == 0 && timer_.mode && timer_.ext_pair(Op::kApplyName, &e0, &e1);
-                if (!ev) tbegin(Op::kApplyName);
-                op_->apply_sums(part, p_, Ap_, lm_ ? CtC_ : nullptr, stop, rs, r_, w, stream_, e0, e1);
-                if (ev) timer_.ext_record(Op::kApplyName, e0, e1);
-                else tend();
-            };
-            if (split) {
-                halo_mark();
-                launch(1);
-                halo_begin(comm_, vec_planes(p_), dom_, op_->halo());
-                halo_join();
-                launch(2);
-            } else {
-                exchange_vec(p_);
-                launch(0);
-            }
+            const ZetaArgs z = zeta_args(i);
+            pcg_apply_sums(i, stop);
             if (distributed()) {
                 allreduce(pending ? rz(i) : pap(i), pending ? 6 : 4);
-                if (pending && lm_)   // the previous iteration's exit test on the global q
-                    hipLaunchKernelGGL((zeta_kernel<T>), dim3(1), dim3(1), 0, stream_, red_.scalars, q(i),
-                                       red_.scalars + kScQ0, i - 1, sp_.q_tolerance, stop_);
+                if (pending && lm_) pcg_zeta(i - 1);   // the previous iteration's exit test on the global q
                 pending = false;
             }
-            const bool reset = lm_ && ((i + 1) % std::max(1, sp_.residual_reset_period)) == 0;
-            if (reset) {   // the classic halves with step23's guards (a zero step / beta = 0)
-                hipLaunchKernelGGL((half1_kernel<T, true>), dim3(fg()), dim3(kBlock), 0, stream_, n_, (const T*)p_, delta_,
-                                   red_.scalars, rz(i), pap(i), stop);
-                exchange_vec(delta_);
-                op_->apply(delta_, Adelta_, CtC_, stop, red_.slot(nb(), kScTmp), stream_);
-                hipLaunchKernelGGL((half2_kernel<T>), dim3(fg()), dim3(kBlock), 0, stream_, n_, (const T*)Adelta_,
-                                   (const T*)b_, (const T*)pre_, (const T*)delta_, r_, use_pre, stop,
-                                   red_.slot(fg(), rz(i + 1)), z);
+            if (reset_iteration(i)) {   // the classic halves with step23's guards (a zero step / beta = 0)
+                pcg_half1<true>(i, stop);
+                pcg_reset_apply(stop);
+                pcg_half2(i, stop, z);
                 allreduce(rz(i + 1), 2);
-                tbegin("step3");
-                hipLaunchKernelGGL((step3_kernel<T, 0, true>), dim3(fg()), dim3(kBlock), 0, stream_, n_,
-                                   (const T*)pre_, (const T*)r_, p_, red_.scalars, rz(i + 1), rz(i), use_pre, stop);
-                tend();
-                if (!z.on)
-                    hipLaunchKernelGGL((zeta_kernel<T>), dim3(1), dim3(1), 0, stream_, red_.scalars, q(i + 1),
-                                       red_.scalars + kScQ0, i, sp_.q_tolerance, stop_);
+                pcg_step3<true>(i, stop);
+                if (!z.on) pcg_zeta(i);
                 OPT_HIP_CHECK(hipGetLastError());
                 continue;
             }
-            tbegin("step23");
-            const ReduceSlot rs2 = red_.slot(fg(), rz(i + 1));
-#define S23(F, L)                                                                                              \
-    hipLaunchKernelGGL((step23_kernel<T, F, L>), dim3(fg()), dim3(kBlock), 0, stream_, n_, p_, (const T*)Ap_,      \
-                       (const T*)pre_, (const T*)b_, r_, delta_, red_.scalars, rz(i), rz(i + 1) + 6, use_pre, stop, rs2, \
-                       z)
-            if (i == 0 && lm_) S23(true, true);
-            else if (lm_) S23(false, true);
-            else if (i == 0) S23(true, false);
-            else S23(false, false);
-#undef S23
-            OPT_HIP_CHECK(hipGetLastError());
-            tend();
+            pcg_step23(i, stop, z);
             if (distributed()) pending = true;
         }
     }
@@ -728,26 +544,8 @@ public:
     int apply_preconditioner(void** params, const void* rin, void* zout) override {
         begin_call();
         prepare(params);
-        const int use_pre = spec_.use_preconditioner ? 1 : 0;
-        const long long lo = pix_lo(), hi = pix_hi();
         red_.ensure(std::max(op_->stencil_blocks(), 4096), 4, kScBase + kSlots * (std::max(0, sp_.lIterations) + 2));
-        op_->jtf(r_, diag_, flags_, stream_);
-        exchange({{(void*)flags_, (size_t)dom_.W}});
-        if (!lm_) {
-            hipLaunchKernelGGL((gn_init_kernel<T>), dim3(fg()), dim3(kBlock), 0, stream_, L_, (const uint8_t*)flags_,
-                               r_, (const T*)diag_, pre_, p_, use_pre, lo, hi, red_.slot(fg(), kScTmp));
-        } else {
-            LMScalars lm{initialised_ ? radius_ : sp_.trust_region_radius, sp_.min_lm_diagonal, sp_.max_lm_diagonal};
-            if (!initialised_ || n_iter_ == 0)
-                hipLaunchKernelGGL((lm_init_kernel<T, true>), dim3(fg()), dim3(kBlock), 0, stream_, L_,
-                                   (const uint8_t*)flags_, r_, (const T*)diag_, SSq_, CtC_, pre_, b_, p_,
-                                   use_pre, lm, lo, hi, red_.slot(fg(), kScTmp));
-            else
-                hipLaunchKernelGGL((lm_init_kernel<T, false>), dim3(fg()), dim3(kBlock), 0, stream_, L_,
-                                   (const uint8_t*)flags_, r_, (const T*)diag_, SSq_, CtC_, pre_, b_, p_,
-                                   use_pre, lm, lo, hi, red_.slot(fg(), kScTmp));
-        }
-        OPT_HIP_CHECK(hipGetLastError());
+        linear_init(kScTmp, false);
         schur_prepare(false);   // (a Schur plan's eliminated blocks: inverted by their own rule)
         bool blk = false;
         if constexpr (HasBlockPre<Op>::value)
@@ -968,26 +766,40 @@ private:
     // scalar init kernel as in step(), then schur_prepare without the right-hand side
     void reduced_prepare(void** params) {
         prepare(params);
-        const int use_pre = spec_.use_preconditioner ? 1 : 0;
-        const long long lo = pix_lo(), hi = pix_hi();
         red_.ensure(std::max(op_->stencil_blocks(), 4096), 4, kScBase + kSlots * (std::max(0, sp_.lIterations) + 2));
+        linear_init(kScTmp, false);   // (its flag exchange is idle here: Eliminate refuses row slabs)
+        schur_prepare(false);
+    }
+
+    // The linear system of a Step at the current unknowns (PCGInit1 + LM's diagonal): r_ = -J^T F,
+    // diag(J^T J) and the flags, the neighbours' flags, then pre_, p_0 (LM: b_, CtC_, SSq_ too)
+    // and rz_0 into slot `out`. `timed`: step()'s brackets; the stand-alone entry points add
+    // nothing to the timer. LM takes the plan's current radius (the parameter's before init)
+    // and, until the first step is taken, the FIRST form, which saves SSq (PCGSaveSSq).
+    void linear_init(int out, bool timed) {
+        const long long lo = pix_lo(), hi = pix_hi();
+        const ReduceSlot rs = red_.slot(fg(), out);
+        if (timed) tbegin("jtf");
         op_->jtf(r_, diag_, flags_, stream_);
+        if (timed) tend();
+        exchange({{(void*)flags_, (size_t)dom_.W}});
+        if (timed) tbegin(lm_ ? "lm_init" : "gn_init");
         if (!lm_) {
             hipLaunchKernelGGL((gn_init_kernel<T>), dim3(fg()), dim3(kBlock), 0, stream_, L_, (const uint8_t*)flags_,
-                               r_, (const T*)diag_, pre_, p_, use_pre, lo, hi, red_.slot(fg(), kScTmp));
+                               r_, (const T*)diag_, pre_, p_, use_pre(), lo, hi, rs);
         } else {
             LMScalars lm{initialised_ ? radius_ : sp_.trust_region_radius, sp_.min_lm_diagonal, sp_.max_lm_diagonal};
             if (!initialised_ || n_iter_ == 0)
                 hipLaunchKernelGGL((lm_init_kernel<T, true>), dim3(fg()), dim3(kBlock), 0, stream_, L_,
                                    (const uint8_t*)flags_, r_, (const T*)diag_, SSq_, CtC_, pre_, b_, p_,
-                                   use_pre, lm, lo, hi, red_.slot(fg(), kScTmp));
+                                   use_pre(), lm, lo, hi, rs);
             else
                 hipLaunchKernelGGL((lm_init_kernel<T, false>), dim3(fg()), dim3(kBlock), 0, stream_, L_,
                                    (const uint8_t*)flags_, r_, (const T*)diag_, SSq_, CtC_, pre_, b_, p_,
-                                   use_pre, lm, lo, hi, red_.slot(fg(), kScTmp));
+                                   use_pre(), lm, lo, hi, rs);
         }
+        if (timed) tend();
         OPT_HIP_CHECK(hipGetLastError());
-        schur_prepare(false);
     }
     // explicit plans: the pattern of S for the graphs as bound (host; a no-op while the wiring
     // stands). A rebuild moves the SpMV's buffers, so no captured loop survives it.
@@ -1042,6 +854,189 @@ private:
         return false;
     }
 
+    // ---- the stages of one PCG iteration (pcg_loop, pcg_loop_fused): each picks its variant
+    // and returns. Slots of iteration i: rz(i), pap(i) in, rz(i + 1) / q(i + 1) out.
+    int use_pre() const { return spec_.use_preconditioner ? 1 : 0; }
+    ZetaArgs zeta_args(int i) const {
+        return ZetaArgs{red_.scalars + kScQ0, stop_, i, sp_.q_tolerance, (lm_ && !distributed()) ? 1 : 0};
+    }
+    bool reset_iteration(int i) const { return lm_ && ((i + 1) % std::max(1, sp_.residual_reset_period)) == 0; }
+    // the apply as interior + boundary launches around the halo refresh of p
+    bool halo_split() const {
+        if constexpr (HasApplySplit<Op>::value)
+            return distributed() && overlap_ && comm_->concurrent_halo() && !mat_ && op_->can_split();
+        return false;
+    }
+    // PCGStep3 folded into the next apply (HasFusedStep3). Never on a block plan: tested here,
+    // before step3_fused and apply_prepared are, so the block stages' z is not bypassed.
+    bool fuse3() const {
+        if constexpr (HasFusedStep3<Op>::value) return !distributed() && !mat_ && !block_ && fuse3_on_;
+        return false;
+    }
+    // GN with step3_kernel: the delta update rides in PCGStep3 (reads p_old anyway)
+    bool delta3() const { return !lm_ && delta3_on_ && !fuse3(); }
+
+    // PCGStep1: Ap_ = A p_ and p.Ap into pap(i), by the first variant that holds. Only the
+    // split variant refreshes p's halo itself; every other one needs it done before.
+    void pcg_apply(int i, const int* stop) {
+        const T* dadd = lm_ ? CtC_ : nullptr;
+        const ReduceSlot rs = red_.slot(nb(), pap(i));
+        if constexpr (HasApplySplit<Op>::value)
+            if (halo_split()) {
+                // halo refresh of p beside the interior blocks (Plan::halo_mark/begin/join)
+                tbegin(Op::kApplyName);
+                halo_mark();
+                op_->apply_split(1, p_, Ap_, dadd, stop, rs, stream_);
+                halo_begin(comm_, vec_planes(p_), dom_, op_->halo());
+                halo_join();
+                op_->apply_split(2, p_, Ap_, dadd, stop, rs, stream_);
+                tend();
+                return;
+            }
+        exchange_vec(p_);
+        if (mat_) {
+            // cusparseInner + PCGStep1_Finish (:2101-2118): the SpMV replaces PCGStep1;
+            // as in the reference, the LM CtC term is not part of this product
+            mat_apply(p_, Ap_, stop, pap(i));
+            return;
+        }
+        if constexpr (HasFusedStep3<Op>::value)
+            if (i > 0 && fuse3()) {   // step3 of i-1 already ran the apply's first pass
+                tbegin(Op::kApplyName);
+                op_->apply_prepared(p_, Ap_, dadd, stop, rs, stream_);
+                tend();
+                return;
+            }
+        if constexpr (HasApplyExt<Op>::value) {
+            hipEvent_t e0 = nullptr, e1 = nullptr;
+            if (timer_.mode && timer_.ext_pair(Op::kApplyName, &e0, &e1)) {
+                op_->apply_ext(p_, Ap_, dadd, stop, rs, stream_, e0, e1);
+                timer_.ext_record(Op::kApplyName, e0, e1);
+                return;
+            }
+        }
+        if (schur_apply(p_, Ap_, dadd, stop, rs)) return;
+        tbegin(Op::kApplyName);
+        op_->apply(p_, Ap_, dadd, stop, rs, stream_);
+        tend();
+    }
+    // the fused loop's PCGStep1: the apply with its four sums (HasApplySums) into pap(i) and the
+    // three slots after it, split around the halo refresh of p where pcg_apply would be
+    void pcg_apply_sums(int i, const int* stop) {
+        const T* w = use_pre() ? pre_ : nullptr;   // PCGStep2's weighting W (1 without a preconditioner)
+        const ReduceSlot rs = red_.slot(nb(), pap(i));
+        auto launch = [&](int part) {
+            hipEvent_t e0 = nullptr, e1 = nullptr;
+            const bool ev = part == 0 && timer_.mode && timer_.ext_pair(Op::kApplyName, &e0, &e1);
+            if (!ev) tbegin(Op::kApplyName);
+            op_->apply_sums(part, p_, Ap_, lm_ ? CtC_ : nullptr, stop, rs, r_, w, stream_, e0, e1);
+            if (ev) timer_.ext_record(Op::kApplyName, e0, e1);
+            else tend();
+        };
+        if (halo_split()) {
+            halo_mark();
+            launch(1);
+            halo_begin(comm_, vec_planes(p_), dom_, op_->halo());
+            halo_join();
+            launch(2);
+        } else {
+            exchange_vec(p_);
+            launch(0);
+        }
+    }
+    // PCGStep2: alpha, delta += alpha p (unless it rides in step3), r -= alpha Ap, z, rz / q
+    void pcg_step2(int i, const int* stop, const ZetaArgs& z) {
+        if constexpr (HasBlockPre<Op>::value)
+            if (block_) {
+                tbegin("blk_step2");
+                op_->block_step2(p_, Ap_, b_, r_, delta_, z_, red_.scalars, rz(i), pap(i), i == 0 ? 1 : 0,
+                                 lm_ ? 1 : 0, (lm_ || !delta3()) ? 1 : 0, stop, red_.slot(nb(), rz(i + 1)), z, stream_);
+                tend();
+                return;
+            }
+        tbegin("step2");
+        launch_step2(i == 0, rz(i), pap(i), rz(i + 1), stop, z, !delta3());
+        tend();
+    }
+    // PCGStep2 + PCGStep3 as one pass (the fused loop)
+    void pcg_step23(int i, const int* stop, const ZetaArgs& z) {
+        tbegin("step23");
+        const ReduceSlot rs2 = red_.slot(fg(), rz(i + 1));
+#define S23(F, L)                                                                                              \
+    hipLaunchKernelGGL((step23_kernel<T, F, L>), dim3(fg()), dim3(kBlock), 0, stream_, n_, p_, (const T*)Ap_,      \
+                       (const T*)pre_, (const T*)b_, r_, delta_, red_.scalars, rz(i), rz(i + 1) + 6, use_pre(), stop, rs2, \
+                       z)
+        if (i == 0 && lm_) S23(true, true);
+        else if (lm_) S23(false, true);
+        else if (i == 0) S23(true, false);
+        else S23(false, false);
+#undef S23
+        OPT_HIP_CHECK(hipGetLastError());
+        tend();
+    }
+    // A residual-reset iteration (LM) in place of step2: delta += alpha p, then r = b - A delta
+    // from an apply of delta itself (always matrix-free, unsplit and untimed), z, rz / q.
+    // GUARD: the fused loop's form of the division, as step23_kernel has it.
+    template <bool GUARD>
+    void pcg_half1(int i, const int* stop) {
+        hipLaunchKernelGGL((half1_kernel<T, GUARD>), dim3(fg()), dim3(kBlock), 0, stream_, n_, (const T*)p_, delta_,
+                           red_.scalars, rz(i), pap(i), stop);
+    }
+    void pcg_reset_apply(const int* stop) {
+        exchange_vec(delta_);
+        if (!schur_apply(delta_, Adelta_, CtC_, stop, red_.slot(nb(), kScTmp)))
+            op_->apply(delta_, Adelta_, CtC_, stop, red_.slot(nb(), kScTmp), stream_);
+    }
+    void pcg_half2(int i, const int* stop, const ZetaArgs& z) {
+        if constexpr (HasBlockPre<Op>::value)
+            if (block_) {
+                tbegin("blk_half2");
+                op_->block_half2(Adelta_, b_, delta_, r_, z_, stop, red_.slot(nb(), rz(i + 1)), z, stream_);
+                tend();
+                return;
+            }
+        hipLaunchKernelGGL((half2_kernel<T>), dim3(fg()), dim3(kBlock), 0, stream_, n_, (const T*)Adelta_,
+                           (const T*)b_, (const T*)pre_, (const T*)delta_, r_, use_pre(), stop,
+                           red_.slot(fg(), rz(i + 1)), z);
+    }
+    // PCGStep3 folded into the Op's next apply; false where there is no such thing
+    bool pcg_step3_fused(int i, const int* stop) {
+        if constexpr (HasFusedStep3<Op>::value)
+            if (fuse3()) {
+                tbegin("step3");
+                op_->step3_fused(pre_, r_, p_, red_.scalars, rz(i + 1), rz(i), use_pre(), stop, stream_);
+                tend();
+                return true;
+            }
+        (void)i; (void)stop;
+        return false;
+    }
+    // PCGStep3: p = z + beta p, on the block stages' z_ as it is, else on pre_ r_ (or r_); with
+    // delta3() also GN's delta update, written at i = 0 and added to after. GUARD (the fused
+    // loop's reset iterations, LM: no delta here) as for pcg_half1.
+    template <bool GUARD>
+    void pcg_step3(int i, const int* stop) {
+        const T* zs = block_ ? z_ : r_;
+        const int up = block_ ? 0 : use_pre();
+        const int dm = delta3() ? (i == 0 ? 1 : 2) : 0;
+        tbegin("step3");
+#define S3(DM)                                                                                                   \
+    hipLaunchKernelGGL((step3_kernel<T, DM, GUARD>), dim3(fg()), dim3(kBlock), 0, stream_, n_, (const T*)pre_, zs, p_, \
+                       red_.scalars, rz(i + 1), rz(i), up, stop, DM ? delta_ : nullptr, DM ? rz(i) : 0,          \
+                       DM ? pap(i) : 0)
+        if constexpr (GUARD) S3(0);
+        else if (dm == 1) S3(1);
+        else if (dm == 2) S3(2);
+        else S3(0);
+#undef S3
+        tend();
+    }
+    // LM's exit test on q(i + 1) as its own launch, where no kernel carries it (ZetaArgs::on == 0)
+    void pcg_zeta(int i) {
+        hipLaunchKernelGGL((zeta_kernel<T>), dim3(1), dim3(1), 0, stream_, red_.scalars, q(i + 1),
+                           red_.scalars + kScQ0, i, sp_.q_tolerance, stop_);
+    }
+
     // bind + unknown halo + ComputedArrays, for the standalone entry points
     void prepare(void** params) {
         op_->bind(params, stream_);
@@ -1089,12 +1084,11 @@ private:
     void launch_step2(bool first, int i_num, int i_den, int out, const int* stop, ZetaArgs z = {},
                       bool delta = true) {
         const int g = fg();
-        const int use_pre = spec_.use_preconditioner ? 1 : 0;
         auto slot = red_.slot(g, out);
 #define S2(F, LMV, D)                                                                                  \
     hipLaunchKernelGGL((step2_kernel<T, F, LMV, D>), dim3(g), dim3(kBlock), 0, stream_, n_, (const T*)p_, \
                        (const T*)Ap_, (const T*)pre_, (const T*)b_, r_, delta_, red_.scalars, i_num,    \
-                       i_den, use_pre, stop, slot, z)
+                       i_den, use_pre(), stop, slot, z)
         if (first && lm_) S2(true, true, true);
         else if (lm_) S2(false, true, true);
         else if (!delta) S2(false, false, false);
@@ -1175,14 +1169,14 @@ private:
     bool capturing_ = false;
     const bool graph_off_ = getenv("OPT_AMD_NO_GRAPH") && atoi(getenv("OPT_AMD_NO_GRAPH"));
     const bool overlap_ = env_int("OPT_AMD_HALO_OVERLAP", 1) != 0;   // 0: blocking halo before each apply
-    const bool fuse3_on_ = env_int("OPT_AMD_FUSE_STEP3", 1) != 0;
+    const bool fuse3_on_ = env_int("OPT_AMD_FUSE_STEP3", 1) != 0;   // 0: step3_kernel + the whole apply
     // Ops with apply_sums: OPT_AMD_FUSE23=0 the classic apply / step2 / step3 loop, 1 the
     // fused loop, 2 (default) the fused loop on row slabs only. One GPU, shape_from_shading
     // 4096^2 LM: the apply with the four sums takes 175 us against 131 (r read back, 6
     // instead of 7 waves per SIMD), more than step3's pass saves: 3.56 vs 3.36 ms per step
-    // (tools/r03_fuse23.sh). On slabs the fused loop saves an all-reduce per iteration.
+    // (tools/history/r03_fuse23.sh). On slabs the fused loop saves an all-reduce per iteration.
     const int fuse23_ = env_int("OPT_AMD_FUSE23", 2);
-    const bool delta3_on_ = env_int("OPT_AMD_DELTA_IN_STEP3", 1) != 0;   // 0: delta updated by step2    // 0: step3_kernel + the whole apply
+    const bool delta3_on_ = env_int("OPT_AMD_DELTA_IN_STEP3", 1) != 0;   // 0: delta updated by step2
     std::unique_ptr<MaterializedJacobian<T>> mat_;
     unsigned long long mat_generation_ = 0;    // Op::topology_generation() mat_'s patterns were built for
     float radius_ = 1e4f, decrease_ = 2.0f;
