@@ -133,6 +133,39 @@ int OptAMD_SchurPattern(long long nEliminated, long long nRetained, int nLists, 
                         const int* const* retVertex, const long long* nEdges, long long* counts, int* rowPtr,
                         int* colInd, int* pairPtr, int* pairs, char* buf, int buflen);
 
+/* The explicitly formed normal matrix: NormalMatrix("explicit") in an energy file whose unknowns
+ * lie over one index space makes the plan assemble H = J^T J once per Step in block-CSR (blocks
+ * of blockDim x blockDim, blockDim the channels of all unknowns of one element, row-major inside
+ * a block; rows and columns are elements, columns ascending, every diagonal block present) and
+ * run every apply of PCG, and OptAMD_ApplyJTJ, as a block SpMV. The statement turns the block
+ * preconditioner on, as UsePreconditioner("block") does. LM's diagonal is not part of H (the
+ * apply adds it); excluded elements keep their rows and columns in H (the apply masks the rows).
+ * The pattern follows the graphs' vertex arrays as bound and is rebuilt when they are re-wired
+ * between Steps. NormalMatrix("matrix_free"), or no statement, is the gather apply. Shapes the
+ * explicit form does not take are refused by Opt_ProblemPlan by name, as are
+ * useMaterializedJTJ / useFusedJTJ on such a plan; a file with Eliminate uses ReducedSystem.
+ *
+ * Returns 1 and the shape on such a plan once the graphs have been bound (by Init, Step, or any
+ * entry point that takes problemparams), 0 on any other plan or before, -1 for NULL. */
+int OptAMD_PlanNormalMatrixShape(Opt_Plan* plan, long long* blockRows, int* blockDim, long long* nnzBlocks);
+
+/* H assembled at the bound unknowns, copied into caller device arrays: rowPtr blockRows + 1,
+ * colInd nnzBlocks, val nnzBlocks * blockDim^2 in the plan's precision. With all three NULL the
+ * call binds the arrays and builds the pattern only, so that OptAMD_PlanNormalMatrixShape can
+ * size them. Returns 0, or 1 on a plan without an explicit normal matrix. */
+int OptAMD_NormalMatrix(Opt_Plan* plan, void** problemparams, int* rowPtr, int* colInd, void* val);
+
+/* The symbolic phase behind that pattern, on the host from index arrays alone (no device): graph
+ * g has graphEdges[g] edges; list l is one slot of graph listGraph[l] over the unknowns' space,
+ * vertex[l][e] its vertex at edge e. Instance positions: list after list, edge e of a list at
+ * its base + e. For every edge, every ordered pair of two different instances (q1, q2), in the
+ * order [list, edge], goes to block (vertex(q1), vertex(q2)). Every output may be NULL; counts
+ * receives {instances, pairs, blocks}; pairPtr has blocks + 1 entries and pairs two positions
+ * per pair. Returns 0, or -1 with the cause in buf. */
+int OptAMD_NormalPattern(long long nVertices, int nLists, const int* const* vertex, const int* listGraph,
+                         const long long* graphEdges, int nGraphs, long long* counts, int* rowPtr, int* colInd,
+                         int* pairPtr, int* pairs, char* buf, int buflen);
+
 /* Ap = J^T J p at the current unknowns (+ CtC*p for LM plans, with the CtC of the
  * last LM step) and *p_dot_Ap = p.Ap (reference kernels.PCGStep1,
  * solverGPUGaussNewton.t:607-632, with fmap.applyJTJ o.t:2770-2830). Excluded

@@ -106,6 +106,13 @@ _SIGNATURES = [
                                            ctypes.POINTER(_VP), ctypes.POINTER(ctypes.c_longlong),
                                            ctypes.POINTER(ctypes.c_longlong), _VP, _VP, _VP, _VP, ctypes.c_char_p,
                                            ctypes.c_int]),
+    ("OptAMD_PlanNormalMatrixShape", ctypes.c_int, [_VP, ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_int),
+                                                    ctypes.POINTER(ctypes.c_longlong)]),
+    ("OptAMD_NormalMatrix", ctypes.c_int, [_VP, ctypes.POINTER(_VP), _VP, _VP, _VP]),
+    ("OptAMD_NormalPattern", ctypes.c_int, [ctypes.c_longlong, ctypes.c_int, ctypes.POINTER(_VP), ctypes.POINTER(ctypes.c_int),
+                                            ctypes.POINTER(ctypes.c_longlong), ctypes.c_int,
+                                            ctypes.POINTER(ctypes.c_longlong), _VP, _VP, _VP, _VP, ctypes.c_char_p,
+                                            ctypes.c_int]),
     ("OptAMD_GenericCompileCheck", ctypes.c_int, [ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]),
 ]
 EXPORTED_SYMBOLS = [s[0] for s in _SIGNATURES]
@@ -360,6 +367,34 @@ class OptSolver:
             raise OptError("OptAMD_ReducedMatrix failed")
         return row_ptr, col_ind[:nnzb], val[:nnzb]
 
+    def normal_matrix_shape(self):
+        """(block rows, block dimension, blocks) of the explicitly formed H = J^T J once the
+        graphs are bound (OptAMD_PlanNormalMatrixShape); None on any other plan, or before."""
+        rows, dim, nnzb = ctypes.c_longlong(), ctypes.c_int(), ctypes.c_longlong()
+        k = self.lib.OptAMD_PlanNormalMatrixShape(self.plan, ctypes.byref(rows), ctypes.byref(dim), ctypes.byref(nnzb))
+        if k < 0:
+            raise OptError("OptAMD_PlanNormalMatrixShape failed")
+        return (rows.value, dim.value, nnzb.value) if k == 1 else None
+
+    def normal_matrix(self, problem_params):
+        """H = J^T J assembled at the bound unknowns, in block-CSR (OptAMD_NormalMatrix on a plan
+        whose energy has NormalMatrix("explicit")): (rowPtr, colInd, val[nnzb, C, C]) as torch
+        tensors on the plan's device."""
+        import torch
+        pk = ParamPack(problem_params)
+        if self.lib.OptAMD_NormalMatrix(self.plan, pk.ptr, None, None, None):
+            self._raise_plan_error()
+            raise OptError("OptAMD_NormalMatrix failed (the plan has no explicit normal matrix)")
+        rows, dim, nnzb = self.normal_matrix_shape()
+        row_ptr = torch.empty(rows + 1, dtype=torch.int32, device="cuda")
+        col_ind = torch.empty(max(nnzb, 1), dtype=torch.int32, device="cuda")
+        val = torch.empty((max(nnzb, 1), dim, dim), dtype=torch.float64 if self.double_precision else torch.float32,
+                          device="cuda")
+        if self.lib.OptAMD_NormalMatrix(self.plan, pk.ptr, _ptr(row_ptr), _ptr(col_ind), _ptr(val)):
+            self._raise_plan_error()
+            raise OptError("OptAMD_NormalMatrix failed")
+        return row_ptr, col_ind[:nnzb], val[:nnzb]
+
     def eval_cost(self, problem_params) -> float:
         pk = ParamPack(problem_params)
         c = self.lib.OptAMD_EvalCost(self.state, self.plan, pk.ptr)
@@ -554,6 +589,34 @@ def schur_pattern(n_eliminated: int, n_retained: int, lists):
     pair_ptr, pairs = np.zeros(nnzb + 1, np.int32), np.zeros((npairs, 2), np.int32)
     if lib.OptAMD_SchurPattern(n_eliminated, n_retained, k, evp, rvp, ne, counts, row_ptr.ctypes.data, col_ind.ctypes.data,
                                pair_ptr.ctypes.data, pairs.ctypes.data, buf, 512):
+        raise OptError(buf.value.decode())
+    return {"instances": nq, "pairs": npairs, "blocks": nnzb}, row_ptr, col_ind, pair_ptr, pairs
+
+
+def normal_pattern(n_vertices: int, lists, graph_edges=None):
+    """Symbolic phase of the explicitly formed J^T J on the host (OptAMD_NormalPattern). lists:
+    one vertex array per slot over the unknowns' space, or (graph, vertex array) pairs with
+    graph_edges the edge count of each graph. Returns (counts {instances, pairs, blocks},
+    rowPtr, colInd, pairPtr, pairs[npairs, 2])."""
+    import numpy as np
+    lib = load_library()
+    if graph_edges is None:
+        lists = [(0, v) for v in lists]
+        graph_edges = [len(lists[0][1])] if lists else []
+    vs = [np.ascontiguousarray(v, np.int32) for _, v in lists]
+    k, ng = len(lists), len(graph_edges)
+    vp = (_VP * max(k, 1))(*[a.ctypes.data for a in vs])
+    lg = (ctypes.c_int * max(k, 1))(*[g for g, _ in lists])
+    ge = (ctypes.c_longlong * max(ng, 1))(*graph_edges)
+    counts = (ctypes.c_longlong * 3)()
+    buf = ctypes.create_string_buffer(512)
+    if lib.OptAMD_NormalPattern(n_vertices, k, vp, lg, ge, ng, counts, None, None, None, None, buf, 512):
+        raise OptError(buf.value.decode())
+    nq, npairs, nnzb = list(counts)
+    row_ptr, col_ind = np.zeros(n_vertices + 1, np.int32), np.zeros(nnzb, np.int32)
+    pair_ptr, pairs = np.zeros(nnzb + 1, np.int32), np.zeros((npairs, 2), np.int32)
+    if lib.OptAMD_NormalPattern(n_vertices, k, vp, lg, ge, ng, counts, row_ptr.ctypes.data, col_ind.ctypes.data,
+                                pair_ptr.ctypes.data, pairs.ctypes.data, buf, 512):
         raise OptError(buf.value.decode())
     return {"instances": nq, "pairs": npairs, "blocks": nnzb}, row_ptr, col_ind, pair_ptr, pairs
 

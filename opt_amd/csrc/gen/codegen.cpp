@@ -906,6 +906,7 @@ GenSource generate(GModel& m, bool dbl, bool off32) {
     emit_block_pcg(cx, o);
     emit_schur(cx, o);
     emit_schur_explicit(cx, o);
+    emit_normal(cx, o);
     char note[128];
     snprintf(note, sizeof(note), "// apply: %s (%.2f residual instances per centred residual)\n",
              gs.has_strip ? "gen_apply_strip" : gs.prefer_tiled ? "gen_apply_tiled" : "gen_apply",

@@ -39,6 +39,12 @@ namespace gen {
 // explicit Schur complement: a block of S with more pairs than this is assembled by a whole
 // workgroup (gen_schur_assemble_long; the host lists such blocks), the others by one wave each
 constexpr int kSchurLongPairs = 128;
+// explicit J^T J: gen_normal_spmv gives a block row to C lanes of a wave, which walk it block
+// after block; a row with more blocks than this (a hub vertex; the host lists such rows) is
+// summed by a whole workgroup instead, the form of gen_schur_spmv. That form pays two barriers
+// and 256 / C values added from LDS by C lanes per row, about what 64 more blocks cost the
+// lane group, whose wave meanwhile waits for its longest row (reasoned, not measured).
+constexpr int kNormalLongRow = 64;
 
 struct GenSource {
     std::string code;
@@ -79,6 +85,15 @@ struct GenSource {
     int schur_cr = 0, schur_ce = 0, schur_rspace = -1;
     struct SchurList { int graph; int eslot; int rslot; };
     std::vector<SchurList> schur_lists;
+    // NormalMatrix("explicit") (codegen_normal.cpp): gen_normal_eblk, gen_normal_assemble and
+    // gen_normal_spmv emitted. C: channels of the one block group, R: residuals per edge (the
+    // largest graph's; G_q is C x R), the group's space. Each list is one slot over that space
+    // of one graph (a GenArgs::slot index); instance e of list l, edge e seen from that slot,
+    // sits at position (sum of the earlier lists' edge counts) + e.
+    bool has_normal = false;
+    int normal_c = 0, normal_r = 0, normal_space = -1;
+    struct NormalList { int graph; int slot; };
+    std::vector<NormalList> normal_lists;
 };
 
 // Generate the kernels for `m` in float (dbl = false) or double. off32: every array a

@@ -229,6 +229,13 @@ void emit_block_pcg(const Ctx& cx, std::ostringstream& o);           // gen_blk_
 void graph_gather(Ctx& cx, std::ostringstream& o, bool apply, int sp, int schur = 0);
 void emit_schur(Ctx& cx, std::ostringstream& o);                     // gen_schur_rhs, gen_schur_elim, gen_schur_apply
 void emit_schur_explicit(Ctx& cx, std::ostringstream& o);            // gen_schur_eblk, gen_schur_assemble, gen_schur_spmv
+// shared by the two explicitly formed matrices (codegen_schur_explicit.cpp): the pair-list
+// assembly kernels `name` / `name`_long, and opt_rbase / opt_rstride, the place of a block
+// group's rows in the unknown vector
+void emit_pair_assemble(std::ostringstream& o, const std::string& name, int CR, int CE, const std::string& Gr, bool minus,
+                        bool packed = false);
+void emit_group_rows(const Ctx& cx, std::ostringstream& o, const GBlockGroup& GR);
+void emit_normal(Ctx& cx, std::ostringstream& o);                    // gen_normal_eblk, gen_normal_assemble, gen_normal_spmv
 
 }  // namespace gen
 }  // namespace optamd

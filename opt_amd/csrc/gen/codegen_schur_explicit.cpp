@@ -34,6 +34,141 @@
 namespace optamd {
 namespace gen {
 
+// The assembly of a block-CSR matrix whose block b is [row = col] B_row (+ or -) the sum over the
+// block's pair list of Y_q1 W_q2^T (Y, W: CR x CE per instance): `name` sums a block with one
+// wave, one lane per entry, `name`_long the blocks with more than kSchurLongPairs pairs (listed by
+// the host) with one workgroup each. minus: the Schur complement's sign; the explicitly formed
+// J^T J (codegen_normal.cpp) adds, with Y = W. Gr: the block group B is packed for.
+// packed: a wave sums 64 / CR^2 blocks at once, lane = (block in the wave, entry), each lane
+// walking its own block's list (J^T J has millions of blocks of two or three pairs; a wave per
+// block leaves most lanes idle). The order inside an entry's sum is the list's either way.
+void emit_pair_assemble(std::ostringstream& o, const std::string& name, int CR, int CE, const std::string& Gr, bool minus,
+                        bool packed) {
+    const char* sign = minus ? "-" : "+";
+    if (packed)
+        o << "extern \"C\" __global__ __launch_bounds__(256) void " << name << "(GenArgs a, const T* __restrict__ blk,\n"
+             "        const T* __restrict__ Wq, const T* __restrict__ Yq, const int* __restrict__ blkRow, const int* __restrict__ colInd,\n"
+             "        const int* __restrict__ pairPtr, const int* __restrict__ pairs, T* __restrict__ val, int nnzb) {\n"
+             "    constexpr int CR = " << CR << ", CE = " << CE << ", CC = CR * CR, CW = CR * CE, NBW = 64 / CC;\n"
+             "    const int lane = threadIdx.x & 63;\n"
+             "    const int bl = lane / CC, ij = lane - bl * CC, i = ij / CR, j = ij - i * CR;\n"
+             "    const long long bN = " << Gr << "::n(a), bB = " << Gr << "::base(a);\n"
+             "    const int tij = i >= j ? i * (i + 1) / 2 + j : j * (j + 1) / 2 + i;\n"
+             "    const long long nw = ((long long)nnzb + NBW - 1) / NBW;\n"
+             "    for (long long g = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); g < nw; g += (long long)gridDim.x * 4) {\n"
+             "        const long long b = g * NBW + bl;\n"
+             "        if (bl >= NBW || b >= nnzb) continue;\n"
+             "        const int row = blkRow[b], col = colInd[b];\n"
+             "        const int p0 = pairPtr[b], p1 = pairPtr[b + 1];\n"
+             "        if (p1 - p0 > " << kSchurLongPairs << ") continue;   // " << name << "_long's\n"
+             "        T acc = row == col ? blk[bB + (long long)tij * bN + row] : (T)0;\n"
+             "#pragma unroll 4\n"
+             "        for (int pp = p0; pp < p1; ++pp) {\n"
+             "            const int q1 = pairs[2LL * pp], q2 = pairs[2LL * pp + 1];\n"
+             "            const T* y = Yq + (long long)q1 * CW + i * CE;\n"
+             "            const T* w = Wq + (long long)q2 * CW + j * CE;\n"
+             "            T s = y[0] * w[0];\n"
+             "#pragma unroll\n"
+             "            for (int c = 1; c < CE; ++c) s += y[c] * w[c];\n"
+             "            acc " << sign << "= s;\n"
+             "        }\n"
+             "        val[b * CC + ij] = acc;\n"
+             "    }\n"
+             "}\n";
+    else
+    o << "extern \"C\" __global__ __launch_bounds__(256) void " << name << "(GenArgs a, const T* __restrict__ blk,\n"
+         "        const T* __restrict__ Wq, const T* __restrict__ Yq, const int* __restrict__ blkRow, const int* __restrict__ colInd,\n"
+         "        const int* __restrict__ pairPtr, const int* __restrict__ pairs, T* __restrict__ val, int nnzb) {\n"
+         "    constexpr int CR = " << CR << ", CE = " << CE << ", CC = CR * CR, CW = CR * CE;\n"
+         "    const int lane = threadIdx.x & 63;\n"
+         "    const int i = lane / CR, j = lane - i * CR;\n"
+         "    const bool on = lane < CC;\n"
+         "    const long long bN = " << Gr << "::n(a), bB = " << Gr << "::base(a);\n"
+         "    const int tij = i >= j ? i * (i + 1) / 2 + j : j * (j + 1) / 2 + i;\n"
+         "    for (long long b = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); b < nnzb; b += (long long)gridDim.x * 4) {\n"
+         "        const int row = blkRow[b], col = colInd[b];\n"
+         "        const int p0 = pairPtr[b], p1 = pairPtr[b + 1];\n"
+         "        if (p1 - p0 > " << kSchurLongPairs << ") continue;   // " << name << "_long's\n"
+         "        T acc = (on && row == col) ? blk[bB + (long long)tij * bN + row] : (T)0;\n"
+         "        if (on) {\n"
+         "#pragma unroll 4\n"
+         "            for (int pp = p0; pp < p1; ++pp) {\n"
+         "                const int q1 = pairs[2LL * pp], q2 = pairs[2LL * pp + 1];\n"
+         "                const T* y = Yq + (long long)q1 * CW + i * CE;\n"
+         "                const T* w = Wq + (long long)q2 * CW + j * CE;\n"
+         "                T s = y[0] * w[0];\n"
+         "#pragma unroll\n"
+         "                for (int c = 1; c < CE; ++c) s += y[c] * w[c];\n"
+         "                acc " << sign << "= s;\n"
+         "            }\n"
+         "            val[b * CC + lane] = acc;\n"
+         "        }\n"
+         "    }\n"
+         "}\n";
+
+    // the blocks with long lists (the hubs' diagonal blocks: one pair per observation), listed by
+    // the host: one workgroup per block, the list dealt to 256 / Cr^2 slices of Cr^2 lanes, the
+    // slices' sums subtracted from (or added to) B in slice order through LDS
+    o << "extern \"C\" __global__ __launch_bounds__(256) void " << name << "_long(GenArgs a, const T* __restrict__ blk,\n"
+         "        const T* __restrict__ Wq, const T* __restrict__ Yq, const int* __restrict__ blkRow, const int* __restrict__ colInd,\n"
+         "        const int* __restrict__ pairPtr, const int* __restrict__ pairs, T* __restrict__ val,\n"
+         "        const int* __restrict__ longBlk, int nlong) {\n"
+         "    constexpr int CR = " << CR << ", CE = " << CE << ", CC = CR * CR, CW = CR * CE, NS = 256 / CC;\n"
+         "    __shared__ T part[256];\n"
+         "    const int t = threadIdx.x;\n"
+         "    const int sl = t / CC, ij = t - sl * CC, i = ij / CR, j = ij - i * CR;\n"
+         "    const long long bN = " << Gr << "::n(a), bB = " << Gr << "::base(a);\n"
+         "    const int tij = i >= j ? i * (i + 1) / 2 + j : j * (j + 1) / 2 + i;\n"
+         "    for (int k = blockIdx.x; k < nlong; k += gridDim.x) {\n"
+         "        const int b = longBlk[k];\n"
+         "        const int row = blkRow[b], col = colInd[b];\n"
+         "        const int p0 = pairPtr[b], p1 = pairPtr[b + 1];\n"
+         "        T acc = 0;\n"
+         "        if (sl < NS) {\n"
+         "#pragma unroll 4\n"
+         "            for (int pp = p0 + sl; pp < p1; pp += NS) {\n"
+         "                const int q1 = pairs[2LL * pp], q2 = pairs[2LL * pp + 1];\n"
+         "                const T* y = Yq + (long long)q1 * CW + i * CE;\n"
+         "                const T* w = Wq + (long long)q2 * CW + j * CE;\n"
+         "                T s = y[0] * w[0];\n"
+         "#pragma unroll\n"
+         "                for (int c = 1; c < CE; ++c) s += y[c] * w[c];\n"
+         "                acc += s;\n"
+         "            }\n"
+         "        }\n"
+         "        part[t] = acc;\n"
+         "        __syncthreads();\n"
+         "        if (t < CC) {\n"
+         "            T s = row == col ? blk[bB + (long long)tij * bN + row] : (T)0;\n"
+         "            for (int h = 0; h < NS; ++h) s " << sign << "= part[h * CC + t];\n"
+         "            val[(long long)b * CC + t] = s;\n"
+         "        }\n"
+         "        __syncthreads();\n"
+         "    }\n"
+         "}\n";
+}
+
+// the place of block row j of group GR in the unknown vector: element e's value is at
+// opt_rbase(a, j) + e * opt_rstride(j)
+void emit_group_rows(const Ctx& cx, std::ostringstream& o, const GBlockGroup& GR) {
+    const GModel& m = cx.m;
+    o << "__device__ __forceinline__ long long opt_rbase(const GenArgs& a, int j) {\n    return ";
+    for (size_t q = 0; q < GR.images.size(); ++q) {
+        const int k = GR.images[q];
+        if (q + 1 < GR.images.size()) o << "j < " << GR.first_row[q] + m.images[k].channels << " ? ";
+        o << "a.uoff[" << cx.uslot[k] << "] + (j - " << GR.first_row[q] << ")";
+        if (q + 1 < GR.images.size()) o << " : ";
+    }
+    o << ";\n}\n__device__ __forceinline__ int opt_rstride(int j) {\n    return ";
+    for (size_t q = 0; q < GR.images.size(); ++q) {
+        const int k = GR.images[q];
+        if (q + 1 < GR.images.size()) o << "j < " << GR.first_row[q] + m.images[k].channels << " ? ";
+        o << m.images[k].channels;
+        if (q + 1 < GR.images.size()) o << " : ";
+    }
+    o << ";\n}\n";
+}
+
 void emit_schur_explicit(Ctx& cx, std::ostringstream& o) {
     if (!cx.schur() || !cx.m.reduced_explicit || !explicit_refusal(cx.m).empty()) return;
     GModel& m = cx.m;
@@ -157,95 +292,10 @@ void emit_schur_explicit(Ctx& cx, std::ostringstream& o) {
     }
     o << "    }\n    }\n}\n";
 
-    // the place of block row j of the retained group in the unknown vector: element e's value
-    // is at opt_rbase(a, j) + e * opt_rstride(j)
-    o << "__device__ __forceinline__ long long opt_rbase(const GenArgs& a, int j) {\n    return ";
-    for (size_t q = 0; q < GR.images.size(); ++q) {
-        const int k = GR.images[q];
-        if (q + 1 < GR.images.size()) o << "j < " << GR.first_row[q] + m.images[k].channels << " ? ";
-        o << "a.uoff[" << cx.uslot[k] << "] + (j - " << GR.first_row[q] << ")";
-        if (q + 1 < GR.images.size()) o << " : ";
-    }
-    o << ";\n}\n__device__ __forceinline__ int opt_rstride(int j) {\n    return ";
-    for (size_t q = 0; q < GR.images.size(); ++q) {
-        const int k = GR.images[q];
-        if (q + 1 < GR.images.size()) o << "j < " << GR.first_row[q] + m.images[k].channels << " ? ";
-        o << m.images[k].channels;
-        if (q + 1 < GR.images.size()) o << " : ";
-    }
-    o << ";\n}\n";
+    emit_group_rows(cx, o, GR);
 
     // ------------------------------------------------------------------ gen_schur_assemble
-    o << "extern \"C\" __global__ __launch_bounds__(256) void gen_schur_assemble(GenArgs a, const T* __restrict__ blk,\n"
-         "        const T* __restrict__ Wq, const T* __restrict__ Yq, const int* __restrict__ blkRow, const int* __restrict__ colInd,\n"
-         "        const int* __restrict__ pairPtr, const int* __restrict__ pairs, T* __restrict__ val, int nnzb) {\n"
-         "    constexpr int CR = " << CR << ", CE = " << CE << ", CC = CR * CR, CW = CR * CE;\n"
-         "    const int lane = threadIdx.x & 63;\n"
-         "    const int i = lane / CR, j = lane - i * CR;\n"
-         "    const bool on = lane < CC;\n"
-         "    const long long bN = " << Gr << "::n(a), bB = " << Gr << "::base(a);\n"
-         "    const int tij = i >= j ? i * (i + 1) / 2 + j : j * (j + 1) / 2 + i;\n"
-         "    for (long long b = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); b < nnzb; b += (long long)gridDim.x * 4) {\n"
-         "        const int row = blkRow[b], col = colInd[b];\n"
-         "        const int p0 = pairPtr[b], p1 = pairPtr[b + 1];\n"
-         "        if (p1 - p0 > " << kSchurLongPairs << ") continue;   // gen_schur_assemble_long's\n"
-         "        T acc = (on && row == col) ? blk[bB + (long long)tij * bN + row] : (T)0;\n"
-         "        if (on) {\n"
-         "#pragma unroll 4\n"
-         "            for (int pp = p0; pp < p1; ++pp) {\n"
-         "                const int q1 = pairs[2LL * pp], q2 = pairs[2LL * pp + 1];\n"
-         "                const T* y = Yq + (long long)q1 * CW + i * CE;\n"
-         "                const T* w = Wq + (long long)q2 * CW + j * CE;\n"
-         "                T s = y[0] * w[0];\n"
-         "#pragma unroll\n"
-         "                for (int c = 1; c < CE; ++c) s += y[c] * w[c];\n"
-         "                acc -= s;\n"
-         "            }\n"
-         "            val[b * CC + lane] = acc;\n"
-         "        }\n"
-         "    }\n"
-         "}\n";
-
-    // the blocks with long lists (the hubs' diagonal blocks: one pair per observation), listed by
-    // the host: one workgroup per block, the list dealt to 256 / Cr^2 slices of Cr^2 lanes, the
-    // slices' sums subtracted from B in slice order through LDS
-    o << "extern \"C\" __global__ __launch_bounds__(256) void gen_schur_assemble_long(GenArgs a, const T* __restrict__ blk,\n"
-         "        const T* __restrict__ Wq, const T* __restrict__ Yq, const int* __restrict__ blkRow, const int* __restrict__ colInd,\n"
-         "        const int* __restrict__ pairPtr, const int* __restrict__ pairs, T* __restrict__ val,\n"
-         "        const int* __restrict__ longBlk, int nlong) {\n"
-         "    constexpr int CR = " << CR << ", CE = " << CE << ", CC = CR * CR, CW = CR * CE, NS = 256 / CC;\n"
-         "    __shared__ T part[256];\n"
-         "    const int t = threadIdx.x;\n"
-         "    const int sl = t / CC, ij = t - sl * CC, i = ij / CR, j = ij - i * CR;\n"
-         "    const long long bN = " << Gr << "::n(a), bB = " << Gr << "::base(a);\n"
-         "    const int tij = i >= j ? i * (i + 1) / 2 + j : j * (j + 1) / 2 + i;\n"
-         "    for (int k = blockIdx.x; k < nlong; k += gridDim.x) {\n"
-         "        const int b = longBlk[k];\n"
-         "        const int row = blkRow[b], col = colInd[b];\n"
-         "        const int p0 = pairPtr[b], p1 = pairPtr[b + 1];\n"
-         "        T acc = 0;\n"
-         "        if (sl < NS) {\n"
-         "#pragma unroll 4\n"
-         "            for (int pp = p0 + sl; pp < p1; pp += NS) {\n"
-         "                const int q1 = pairs[2LL * pp], q2 = pairs[2LL * pp + 1];\n"
-         "                const T* y = Yq + (long long)q1 * CW + i * CE;\n"
-         "                const T* w = Wq + (long long)q2 * CW + j * CE;\n"
-         "                T s = y[0] * w[0];\n"
-         "#pragma unroll\n"
-         "                for (int c = 1; c < CE; ++c) s += y[c] * w[c];\n"
-         "                acc += s;\n"
-         "            }\n"
-         "        }\n"
-         "        part[t] = acc;\n"
-         "        __syncthreads();\n"
-         "        if (t < CC) {\n"
-         "            T s = row == col ? blk[bB + (long long)tij * bN + row] : (T)0;\n"
-         "            for (int h = 0; h < NS; ++h) s -= part[h * CC + t];\n"
-         "            val[(long long)b * CC + t] = s;\n"
-         "        }\n"
-         "        __syncthreads();\n"
-         "    }\n"
-         "}\n";
+    emit_pair_assemble(o, "gen_schur_assemble", CR, CE, Gr, true);
 
     // ------------------------------------------------------------------ gen_schur_spmv
     o << "extern \"C\" __global__ __launch_bounds__(256) void gen_schur_spmv(GenArgs a, const int* __restrict__ rowPtr,\n"

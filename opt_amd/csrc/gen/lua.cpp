@@ -986,6 +986,7 @@ private:
     int lp_counter_ = 0;
     int n_eliminate_ = 0;   // Eliminate statements seen
     int n_reduced_ = 0;     // ReducedSystem statements seen
+    int n_normal_ = 0;      // NormalMatrix statements seen
     void note_index(int idx) { m_->n_params_total = std::max(m_->n_params_total, idx + 1); }
     int channels_of(const Value& t) {
         if (t.k == V::Type) return t.id;
@@ -1285,6 +1286,13 @@ void Interp::install() {
         if (a.size() != 1 || a[0].k != V::Str || (a[0].s != "explicit" && a[0].s != "implicit"))
             err("ReducedSystem(form): form is \"explicit\" or \"implicit\"");
         m_->reduced_explicit = a[0].s == "explicit";
+        return VList{};
+    });
+    def("NormalMatrix", [this](VList& a) {
+        if (++n_normal_ > 1) err("a second NormalMatrix (the normal matrix has one form)");
+        if (a.size() != 1 || a[0].k != V::Str || (a[0].s != "explicit" && a[0].s != "matrix_free"))
+            err("NormalMatrix(form): form is \"explicit\" or \"matrix_free\"");
+        m_->normal_explicit = a[0].s == "explicit";
         return VList{};
     });
     def("Exclude", [this](VList& a) {
@@ -1704,6 +1712,10 @@ void Interp::finish() {
 void Interp::check_eliminate() {
     if (n_reduced_ && m_->eliminated.empty())
         throw LuaError("ReducedSystem: no Eliminate statement (only an energy that eliminates a group has a reduced system)");
+    if (n_normal_ && !m_->eliminated.empty())
+        throw LuaError("NormalMatrix: the energy has an Eliminate statement (its explicitly formed system is "
+                       "ReducedSystem(\"explicit\"))");
+    if (m_->normal_explicit) m_->use_preconditioner = m_->block_preconditioner = true;   // as UsePreconditioner("block")
     if (m_->eliminated.empty()) return;
     const std::vector<int> unk = m_->unknown_images();
     const int sp = m_->images[m_->eliminated[0]].space;
@@ -1793,6 +1805,46 @@ std::string explicit_refusal(const GModel& m) {
                        space_name(kept[0]) + " through two slots ('" + m.graphs[r.graph].slot_names[std::min(slot, n.slot)] +
                        "', '" + m.graphs[r.graph].slot_names[std::max(slot, n.slot)] + "')";
             if (r.graph >= 0) slot = n.slot;
+        }
+    }
+    return "";
+}
+
+// NormalMatrix("explicit"): H = J^T J is the packed diagonal blocks plus, per graph edge, the
+// products of the partials at two of its slots. That is all of H only when every term that is
+// not a graph edge couples an element with itself alone, and one block-CSR matrix only when the
+// unknowns share one space. Arrays and graph slots may lie over any spaces.
+std::string normal_refusal(const GModel& m) {
+    if (!m.normal_explicit || m.schur()) return "";
+    const std::string head = "NormalMatrix(\"explicit\"): ";
+    auto space_name = [&](int sp) {
+        std::string o = "{";
+        for (size_t k = 0; k < m.spaces[sp].size(); ++k) o += (k ? "," : "") + m.dims[m.spaces[sp][k]].name;
+        return o + "}";
+    };
+    const std::vector<int> us = m.unknown_spaces();
+    if (us.size() != 1) {
+        std::string names;
+        for (int sp : us) names += (names.empty() ? "" : ", ") + space_name(sp);
+        return head + "the unknowns lie over " + std::to_string(us.size()) + " index spaces (" + names +
+               "); the block-sparse J^T J has one block group";
+    }
+    auto offset = [](const Node& n) { return n.off[0] != 0 || n.off[1] != 0 || n.off[2] != 0; };
+    for (auto& c : m.computed)
+        for (auto& g : c.grads) {
+            if (g.u < 0) continue;
+            const Node n = m.pool.at(g.u);
+            if (offset(n))
+                return head + "ComputedArray '" + m.images[c.image].name + "' depends on " + m.images[n.i].name +
+                       " at a non-zero offset (J^T J then has blocks no graph edge lists)";
+        }
+    for (auto& r : m.residuals) {
+        if (r.graph >= 0) continue;
+        for (int u : r.unknowns) {
+            const Node n = m.pool.at(u);
+            if (offset(n))
+                return head + "a centred residual over " + space_name(us[0]) + " reads " + m.images[n.i].name +
+                       " at a non-zero offset (J^T J then has blocks no graph edge lists)";
         }
     }
     return "";

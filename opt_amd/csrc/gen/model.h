@@ -95,6 +95,10 @@ struct GModel {
     // PCG's apply is a block SpMV (codegen_schur_explicit.cpp); "implicit" / no statement: the
     // matrix-free apply. The shapes this form takes: explicit_refusal()
     bool reduced_explicit = false;
+    // NormalMatrix("explicit"): H = J^T J is assembled once per step in block-CSR and PCG's apply
+    // is a block SpMV (codegen_normal.cpp); "matrix_free" / no statement: the gather apply. Turns
+    // the block preconditioner on. The shapes this form takes: normal_refusal()
+    bool normal_explicit = false;
     bool schur() const { return elim_space >= 0; }
     bool is_eliminated(int image) const {
         for (int k : eliminated)
@@ -116,6 +120,10 @@ struct GModel {
 // Why ReducedSystem("explicit") cannot serve this model ("" = it can): the retained unknowns
 // must lie over one index space and B, their block of J^T J, must be block-diagonal (lua.cpp).
 std::string explicit_refusal(const GModel& m);
+// Why NormalMatrix("explicit") cannot serve this model ("" = it can): all unknowns must lie over
+// one index space and every centred term must read them at offset 0, so that the diagonal
+// blocks plus the graphs' instance pairs are all of J^T J (lua.cpp).
+std::string normal_refusal(const GModel& m);
 
 // Run `text` (an Opt energy file). false + message on a Lua or DSL error.
 bool build_model(const std::string& text, GModel* m, std::string* err);

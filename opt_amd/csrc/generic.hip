@@ -198,6 +198,8 @@ bool generic_signature(const std::string& text, std::string* sig, bool* use_pre,
              std::to_string(r.unknowns.size()) + ":" + m.pool.str(r.expr) + ";";
     // (only when requested: every other energy's signature is what it always was)
     if (m.block_preconditioner) s += "B;";
+    // NormalMatrix("explicit"): the normal matrix's form ("matrix_free" is no statement)
+    if (m.normal_explicit) s += "NX;";
     // Eliminate: the group's index space (such a file always runs on generated kernels)
     if (m.schur()) s += "S" + std::to_string(m.elim_space) + ";";
     // ReducedSystem("explicit"): the reduced system's form ("implicit" is no statement)
@@ -643,6 +645,113 @@ public:
         for (const void* q : {(const void*)sx_rowptr_, (const void*)sx_colind_, (const void*)sx_val_})
             key->push_back((unsigned long long)(uintptr_t)q);
     }
+    // ---- the explicitly formed H = J^T J (NormalMatrix("explicit"); StencilPlan: HasNormal;
+    // gen/codegen_normal.cpp) ----
+    // Symbolic phase (host, schur_pattern.h with the edge in the eliminated vertex's place):
+    // block-CSR pattern, per-block lists of instance pairs and the long rows, built from the
+    // vertex arrays at the first use and again when the graphs were re-wired. Numeric phase, once
+    // per Step between jtf (the diagonal blocks in blk) and block_init (which inverts them in
+    // place): normal_eblk writes G_q per edge instance, normal_assemble sums the blocks.
+    // normal_spmv then is apply's contract on the assembled matrix. The buffers are the
+    // explicit Schur complement's (sx_*): a file has one of the two statements.
+    bool normal() const { return src_.has_normal; }
+    bool normal_symbolic_stale() const { return !sx_rowptr_ || sx_generation_ != topology_generation_; }
+    void normal_symbolic(hipStream_t s) {
+        if (!normal_symbolic_stale()) return;
+        schur_explicit_release();   // the old wiring's buffers first: both need not fit together
+        if (src_.normal_lists.size() > 16) throw PlanError("generic: NormalMatrix(\"explicit\"): more than 16 instance lists");
+        // the edges of the graphs with lists, numbered graph after graph: edge e of graph g is
+        // "eliminated vertex" ebase[g] + e, and its instance in a list sits at position e
+        long long ebase[4] = {0, 0, 0, 0}, ne = 0;
+        for (size_t g = 0; g < m_.graphs.size() && g < 4; ++g) {
+            bool used = false;
+            for (auto& l : src_.normal_lists) used |= l.graph == (int)g;
+            ebase[g] = ne;
+            if (used) ne += nedge_[g];
+        }
+        std::vector<std::vector<int>> host(src_.normal_lists.size()), ids(src_.normal_lists.size());
+        for (size_t l = 0; l < src_.normal_lists.size(); ++l) {
+            const auto& L = src_.normal_lists[l];
+            host[l].resize(std::max(1, nedge_[L.graph]));
+            OPT_HIP_CHECK(hipMemcpyAsync(host[l].data(), a_.slot[L.slot], sizeof(int) * nedge_[L.graph], hipMemcpyDeviceToHost, s));
+            ids[l].resize(std::max(1, nedge_[L.graph]));
+            for (int e = 0; e < nedge_[L.graph]; ++e) ids[l][e] = (int)(ebase[L.graph] + e);
+        }
+        OPT_HIP_CHECK(hipStreamSynchronize(s));
+        std::vector<SchurList> lists;
+        for (size_t l = 0; l < src_.normal_lists.size(); ++l)
+            lists.push_back({ids[l].data(), host[l].data(), nedge_[src_.normal_lists[l].graph]});
+        const long long nR = pixels_of(groups_[0].images[0]);
+        SchurPattern P;
+        try {
+            schur_pattern_build(ne, nR, lists, &P, true, "NormalMatrix(\"explicit\")");
+        } catch (const std::length_error& e) {
+            throw PlanError(std::string("generic: ") + e.what());
+        }
+        for (size_t l = 0; l < P.base.size(); ++l) sx_qb_.b[l] = P.base[l];
+        sx_nnzb_ = P.n_blocks();
+        sx_npairs_ = P.n_pairs();
+        sx_nq_ = P.n_instances;
+        auto up = [&](const std::vector<int>& v) {
+            int* d = (int*)dmalloc(sizeof(int) * std::max<size_t>(1, v.size()));
+            if (!v.empty()) OPT_HIP_CHECK(hipMemcpyAsync(d, v.data(), sizeof(int) * v.size(), hipMemcpyHostToDevice, s));
+            return d;
+        };
+        sx_rowptr_ = up(P.rowPtr);
+        sx_colind_ = up(P.colInd);
+        sx_blkrow_ = up(P.blkRow);
+        sx_pairptr_ = up(P.pairPtr);
+        sx_pairs_ = up(P.pairs);
+        std::vector<int> lng, lrow;   // blocks left to gen_normal_assemble_long, rows to the SpMV's workgroup form
+        for (long long b = 0; b < sx_nnzb_; ++b)
+            if (P.pairPtr[b + 1] - P.pairPtr[b] > gen::kSchurLongPairs) lng.push_back((int)b);
+        for (long long r = 0; r < nR; ++r)
+            if (P.rowPtr[r + 1] - P.rowPtr[r] > gen::kNormalLongRow) lrow.push_back((int)r);
+        sx_nlong_ = (int)lng.size();
+        sx_long_ = up(lng);
+        nx_nlongrow_ = (int)lrow.size();
+        nx_longrow_ = up(lrow);
+        OPT_HIP_CHECK(hipStreamSynchronize(s));   // (the host vectors go out of scope)
+        const size_t cw = (size_t)src_.normal_c * src_.normal_r, cc = (size_t)src_.normal_c * src_.normal_c;
+        sx_val_ = (T*)dmalloc(sizeof(T) * std::max<size_t>(1, cc * sx_nnzb_));
+        sx_w_ = (T*)dmalloc(sizeof(T) * std::max<size_t>(1, cw * sx_nq_));
+        sx_generation_ = topology_generation_;
+    }
+    void normal_eblk(hipStream_t s) { launch(k_normal_eblk_, s, {&a_, &sx_w_, &sx_qb_}); }
+    void normal_assemble(hipStream_t s) {
+        const int nnzb = (int)sx_nnzb_;
+        const long long per_wg = 4 * (64 / (src_.normal_c * src_.normal_c));   // blocks per workgroup (the packed form)
+        const int grid = (int)std::max<long long>(1, std::min<long long>((sx_nnzb_ + per_wg - 1) / per_wg, 1 << 18));
+        launch_grid(k_normal_assemble_, grid, s, {&a_, &blk_, &sx_w_, &sx_w_, &sx_blkrow_, &sx_colind_, &sx_pairptr_, &sx_pairs_,
+                                                  &sx_val_, &nnzb});
+        if (sx_nlong_ > 0)
+            launch_grid(k_normal_assemble_long_, std::min(sx_nlong_, 1 << 16), s,
+                        {&a_, &blk_, &sx_w_, &sx_w_, &sx_blkrow_, &sx_colind_, &sx_pairptr_, &sx_pairs_, &sx_val_, &sx_long_,
+                         &sx_nlong_});
+    }
+    void normal_spmv(const T* p, T* Ap, const T* dadd, const int* stop, ReduceSlot rs, hipStream_t s) {
+        launch(k_normal_spmv_, s, {&a_, &sx_rowptr_, &sx_colind_, &sx_val_, &p, &Ap, &dadd, &stop, &rs, &nx_longrow_, &nx_nlongrow_});
+    }
+    // block rows, block dimension, blocks; false before the first symbolic phase
+    bool normal_matrix_shape(long long* rows, int* dim, long long* nnzb) const {
+        if (!src_.has_normal || !sx_rowptr_) return false;
+        if (rows) *rows = pixels_of(groups_[0].images[0]);
+        if (dim) *dim = src_.normal_c;
+        if (nnzb) *nnzb = sx_nnzb_;
+        return true;
+    }
+    long long normal_matrix_pairs() const { return sx_npairs_; }
+    void normal_matrix_copy(int* rowPtr, int* colInd, T* val, hipStream_t s) {
+        const long long nR = pixels_of(groups_[0].images[0]);
+        OPT_HIP_CHECK(hipMemcpyAsync(rowPtr, sx_rowptr_, sizeof(int) * (nR + 1), hipMemcpyDefault, s));
+        OPT_HIP_CHECK(hipMemcpyAsync(colInd, sx_colind_, sizeof(int) * sx_nnzb_, hipMemcpyDefault, s));
+        OPT_HIP_CHECK(hipMemcpyAsync(val, sx_val_, sizeof(T) * sx_nnzb_ * src_.normal_c * src_.normal_c, hipMemcpyDefault, s));
+    }
+    // the buffers the captured PCG loop's SpMV bakes in (StencilPlan::pcg_graph_begin)
+    void normal_key(std::vector<unsigned long long>* key) const {
+        for (const void* q : {(const void*)sx_rowptr_, (const void*)sx_colind_, (const void*)sx_val_, (const void*)nx_longrow_})
+            key->push_back((unsigned long long)(uintptr_t)q);
+    }
     void apply(const T* p, T* Ap, const T* dadd, const int* stop, ReduceSlot rs, hipStream_t s) {
         if (!src_.has_graph) {
             int finish = 1;
@@ -796,6 +905,12 @@ private:
                             std::make_pair(&k_schur_spmv_, "gen_schur_spmv")})
                 OPT_HIP_CHECK(hipModuleGetFunction(kv.first, mod_, kv.second));
         }
+        if (src_.has_normal) {
+            for (auto kv : {std::make_pair(&k_normal_eblk_, "gen_normal_eblk"), std::make_pair(&k_normal_assemble_, "gen_normal_assemble"),
+                            std::make_pair(&k_normal_assemble_long_, "gen_normal_assemble_long"),
+                            std::make_pair(&k_normal_spmv_, "gen_normal_spmv")})
+                OPT_HIP_CHECK(hipModuleGetFunction(kv.first, mod_, kv.second));
+        }
         // (the strip J^T F has no block accumulation: block energies keep the gather)
         if (src_.has_jtf_strip && !slab && !m_.block_preconditioner) {
             const char* wj = getenv("OPT_AMD_GEN_JTF");
@@ -828,7 +943,7 @@ private:
         OPT_HIP_CHECK(hipModuleLaunchKernel(f, grid, 1, 1, kBlock, 1, 1, 0, s, a.data(), nullptr));
     }
     void schur_explicit_release() {
-        for (int** q : {&sx_rowptr_, &sx_colind_, &sx_blkrow_, &sx_pairptr_, &sx_pairs_, &sx_long_}) { dfree(*q); *q = nullptr; }
+        for (int** q : {&sx_rowptr_, &sx_colind_, &sx_blkrow_, &sx_pairptr_, &sx_pairs_, &sx_long_, &nx_longrow_}) { dfree(*q); *q = nullptr; }
         for (T** q : {&sx_val_, &sx_w_, &sx_y_}) { dfree(*q); *q = nullptr; }
     }
     // vertex indices must lie in [0, N) (fail-stop, as the reference does on bad input)
@@ -961,10 +1076,16 @@ private:
     long long sx_nnzb_ = 0, sx_npairs_ = 0, sx_nq_ = 0;
     int *sx_rowptr_ = nullptr, *sx_colind_ = nullptr, *sx_blkrow_ = nullptr, *sx_pairptr_ = nullptr, *sx_pairs_ = nullptr;
     T *sx_val_ = nullptr, *sx_w_ = nullptr, *sx_y_ = nullptr;
+    // explicit J^T J: its kernels (pattern, values and G_q live in the sx_ buffers above) and the
+    // rows with more than gen::kNormalLongRow blocks
+    hipFunction_t k_normal_eblk_{}, k_normal_assemble_{}, k_normal_assemble_long_{}, k_normal_spmv_{};
+    int* nx_longrow_ = nullptr;
+    int nx_nlongrow_ = 0;
 };
 
 static_assert(HasBlockPre<GenericOp<float>>::value);   // the optional driver features this Op claims (stencil_plan.h)
 static_assert(HasSchur<GenericOp<float>>::value);
+static_assert(HasNormal<GenericOp<float>>::value);
 static_assert(HasCaptureKey<GenericOp<float>>::value);
 static_assert(HasRefreshCaches<GenericOp<float>>::value);
 static_assert(HasSlabRefusal<GenericOp<float>>::value);
@@ -1001,6 +1122,15 @@ std::unique_ptr<Plan> make_generic_plan(const ProblemSpec& spec, const StateOpti
     {
         const std::string why = gen::explicit_refusal(m);
         if (!why.empty()) { *err = "generic: " + why; return nullptr; }
+    }
+    {
+        const std::string why = gen::normal_refusal(m);
+        if (!why.empty()) { *err = "generic: " + why; return nullptr; }
+    }
+    if (m.normal_explicit && (opts.materialized || opts.fused_jtj)) {
+        *err = "generic: no materialized Jacobian (useMaterializedJTJ / useFusedJTJ) with NormalMatrix(\"explicit\"): "
+               "the plan forms J^T J itself";
+        return nullptr;
     }
     if (m.multi()) {
         if (opts.materialized || opts.fused_jtj) {
@@ -1077,7 +1207,8 @@ int generic_describe(const std::string& text, std::string* out) {
 int generic_plan_check(const std::string& text, std::string* why) {
     gen::GModel m;
     if (!gen::build_model(text, &m, why)) return -1;
-    const std::string r = gen::explicit_refusal(m);
+    std::string r = gen::explicit_refusal(m);
+    if (r.empty()) r = gen::normal_refusal(m);
     if (r.empty()) return 0;
     *why = "generic: " + r;
     return 1;

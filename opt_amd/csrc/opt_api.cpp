@@ -270,6 +270,17 @@ int OptAMD_ReducedMatrix(Opt_Plan* plan, void** params, int* rowPtr, int* colInd
     plan->error.clear();
     return guarded(plan, "OptAMD_ReducedMatrix", 1, [&] { return plan->impl->reduced_matrix(params, rowPtr, colInd, val); });
 }
+int OptAMD_PlanNormalMatrixShape(Opt_Plan* plan, long long* blockRows, int* blockDim, long long* nnzBlocks) {
+    if (!valid_plan(plan, "OptAMD_PlanNormalMatrixShape")) return -1;
+    return plan->impl->normal_matrix_shape(blockRows, blockDim, nnzBlocks) ? 1 : 0;
+}
+int OptAMD_NormalMatrix(Opt_Plan* plan, void** params, int* rowPtr, int* colInd, void* val) {
+    if (!valid_plan(plan, "OptAMD_NormalMatrix")) return 1;
+    const int given = (rowPtr ? 1 : 0) + (colInd ? 1 : 0) + (val ? 1 : 0);
+    if (given != 0 && given != 3) return 1;
+    plan->error.clear();
+    return guarded(plan, "OptAMD_NormalMatrix", 1, [&] { return plan->impl->normal_matrix(params, rowPtr, colInd, val); });
+}
 int OptAMD_ApplyJTJ(Opt_State* state, Opt_Plan* plan, void** params, const void* p, void* Ap,
                     double* pAp) {
     if (!valid_state(state, "OptAMD_ApplyJTJ") || !valid_plan(plan, "OptAMD_ApplyJTJ") || !p || !Ap)
@@ -515,6 +526,44 @@ int OptAMD_SchurPattern(long long nEliminated, long long nRetained, int nLists, 
     optamd::SchurPattern P;
     try {
         optamd::schur_pattern_build(nEliminated, nRetained, lists, &P);
+    } catch (const std::exception& e) {
+        return copy_name(e.what(), buf, n), -1;
+    }
+    if (counts) { counts[0] = P.n_instances; counts[1] = P.n_pairs(); counts[2] = P.n_blocks(); }
+    if (rowPtr) std::copy(P.rowPtr.begin(), P.rowPtr.end(), rowPtr);
+    if (colInd) std::copy(P.colInd.begin(), P.colInd.end(), colInd);
+    if (pairPtr) std::copy(P.pairPtr.begin(), P.pairPtr.end(), pairPtr);
+    if (pairs) std::copy(P.pairs.begin(), P.pairs.end(), pairs);
+    return 0;
+}
+int OptAMD_NormalPattern(long long nVertices, int nLists, const int* const* vertex, const int* listGraph,
+                         const long long* graphEdges, int nGraphs, long long* counts, int* rowPtr, int* colInd,
+                         int* pairPtr, int* pairs, char* buf, int n) {
+    if (nVertices < 0 || nLists < 0 || nGraphs < 0 || (nLists && (!vertex || !listGraph || !graphEdges)))
+        return copy_name("invalid arguments", buf, n), -1;
+    std::vector<long long> ebase(nGraphs + 1, 0);
+    for (int g = 0; g < nGraphs; ++g) {
+        if (graphEdges[g] < 0) return copy_name("invalid arguments", buf, n), -1;
+        ebase[g + 1] = ebase[g] + graphEdges[g];
+    }
+    if (ebase[nGraphs] > 2147483647LL) return copy_name("more than 2^31 - 1 edges", buf, n), -1;
+    std::vector<std::vector<int>> ids(nLists);
+    std::vector<optamd::SchurList> lists;
+    for (int l = 0; l < nLists; ++l) {
+        if (listGraph[l] < 0 || listGraph[l] >= nGraphs)
+            return copy_name("list " + std::to_string(l) + ": no such graph", buf, n), -1;
+        const long long ne = graphEdges[listGraph[l]];
+        ids[l].resize(ne);
+        for (long long e = 0; e < ne; ++e) {
+            if (vertex[l][e] < 0 || vertex[l][e] >= nVertices)
+                return copy_name("list " + std::to_string(l) + ": vertex index outside its space at edge " + std::to_string(e), buf, n), -1;
+            ids[l][e] = (int)(ebase[listGraph[l]] + e);
+        }
+        lists.push_back({ids[l].data(), vertex[l], ne});
+    }
+    optamd::SchurPattern P;
+    try {
+        optamd::schur_pattern_build(ebase[nGraphs], nVertices, lists, &P, true, "NormalMatrix(\"explicit\")");
     } catch (const std::exception& e) {
         return copy_name(e.what(), buf, n), -1;
     }

@@ -180,6 +180,16 @@ public:
         (void)params; (void)rowPtr; (void)colInd; (void)val;
         return 1;
     }
+    // The explicitly formed H = J^T J (NormalMatrix("explicit"), include/opt_amd.h): the same
+    // pair of calls for the normal matrix of a plan whose energy has that statement.
+    virtual bool normal_matrix_shape(long long* rows, int* dim, long long* nnzb) const {
+        (void)rows; (void)dim; (void)nnzb;
+        return false;
+    }
+    virtual int normal_matrix(void** params, int* rowPtr, int* colInd, void* val) {
+        (void)params; (void)rowPtr; (void)colInd; (void)val;
+        return 1;
+    }
 
     void set_solver_param(const char* name, const void* value);
     // the device scalar slots (red_.scalars) to the host, up to n; the count copied

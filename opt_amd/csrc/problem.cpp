@@ -281,6 +281,16 @@ struct Parser {
                     return fail(i, "ReducedSystem(form): form is \"explicit\" or \"implicit\"");
                 if (!spec->reduced_system.empty()) return fail(i, "a second ReducedSystem (the reduced system has one form)");
                 spec->reduced_system = t[a[0].first].text;
+            } else if (f == "NormalMatrix") {
+                // the form of J^T J; "explicit" turns the block preconditioner on. The general
+                // front end checks it against Eliminate (gen/lua.cpp), the plan its shapes
+                args(i + 1, &a);
+                if (a.size() != 1 || !is_single(a[0], Tk::String) ||
+                    (t[a[0].first].text != "explicit" && t[a[0].first].text != "matrix_free"))
+                    return fail(i, "NormalMatrix(form): form is \"explicit\" or \"matrix_free\"");
+                if (!spec->normal_matrix.empty()) return fail(i, "a second NormalMatrix (the normal matrix has one form)");
+                spec->normal_matrix = t[a[0].first].text;
+                if (spec->normal_matrix == "explicit") spec->use_preconditioner = spec->block_preconditioner = true;
             } else if (f == "Exclude") {
                 spec->n_exclude++;
             } else if (f == "ComputedArray") {

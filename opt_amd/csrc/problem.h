@@ -43,6 +43,7 @@ struct ProblemSpec {
     bool block_preconditioner = false;   // UsePreconditioner("block"): generated kernels only
     std::vector<std::string> eliminate;  // Eliminate(X, ...): the group's unknowns (generated kernels only)
     std::string reduced_system;          // ReducedSystem(form): "explicit" / "implicit", "" without the statement
+    std::string normal_matrix;           // NormalMatrix(form): "explicit" / "matrix_free", "" without the statement
     int n_exclude = 0;
     std::vector<std::string> computed_arrays;
     bool uses_sampled_image = false;

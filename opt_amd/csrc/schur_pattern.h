@@ -43,7 +43,14 @@ struct SchurPattern {
 // plan has checked that). Throws std::length_error, naming the counts, when the instances,
 // pairs or blocks exceed 2^31 - 1 (the pair count is known before anything of that size is
 // allocated).
-inline void schur_pattern_build(long long nE, long long nR, const std::vector<SchurList>& lists, SchurPattern* out) {
+//
+// `distinct` (the explicitly formed J^T J of NormalMatrix("explicit"), codegen_normal.cpp): the
+// "eliminated vertex" is the graph edge itself (ev[e] = the edge's number among all graphs'
+// edges), a list is one slot over the unknowns' space, and only the pairs of two DIFFERENT
+// instances are listed: an instance's product with itself is part of the diagonal blocks the
+// J^T F kernels leave. what: the matrix's name in the error message.
+inline void schur_pattern_build(long long nE, long long nR, const std::vector<SchurList>& lists, SchurPattern* out,
+                                bool distinct = false, const char* what = "explicit Schur complement") {
     SchurPattern& S = *out;
     S = SchurPattern();
     long long nq = 0;
@@ -78,11 +85,11 @@ inline void schur_pattern_build(long long nE, long long nR, const std::vector<Sc
     long long np = 0;
     for (long long p = 0; p < nE; ++p) {
         const long long k = off[p + 1] - off[p];
-        np += k * k;
+        np += distinct ? k * (k - 1) : k * k;
     }
     const long long kMax = 2147483647LL;
     if (np > kMax || nq > kMax)
-        throw std::length_error("explicit Schur complement: " + std::to_string(np) + " instance pairs over " +
+        throw std::length_error(std::string(what) + ": " + std::to_string(np) + " instance pairs over " +
                                 std::to_string(nq) + " edge instances (at most 2^31 - 1 of each)");
     // pairs in enumeration order, then stable counting sorts by column and by row
     std::vector<int> pr(np), pc(np), p1(np), p2(np);
@@ -90,8 +97,10 @@ inline void schur_pattern_build(long long nE, long long nR, const std::vector<Sc
         long long at = 0;
         for (long long p = 0; p < nE; ++p)
             for (long long x = off[p]; x < off[p + 1]; ++x)
-                for (long long y = off[p]; y < off[p + 1]; ++y, ++at) {
+                for (long long y = off[p]; y < off[p + 1]; ++y) {
+                    if (distinct && x == y) continue;
                     pr[at] = ir[x]; pc[at] = ir[y]; p1[at] = iq[x]; p2[at] = iq[y];
+                    ++at;
                 }
     }
     std::vector<int> order(np), tmp(np);
@@ -115,7 +124,7 @@ inline void schur_pattern_build(long long nE, long long nR, const std::vector<Sc
         bool diag = false;
         auto open = [&](int col) {
             if ((long long)S.colInd.size() >= kMax)
-                throw std::length_error("explicit Schur complement: more than 2^31 - 1 blocks (" + std::to_string(np) +
+                throw std::length_error(std::string(what) + ": more than 2^31 - 1 blocks (" + std::to_string(np) +
                                         " instance pairs)");
             S.colInd.push_back(col);
             S.blkRow.push_back((int)r);

@@ -104,6 +104,9 @@ __global__ __launch_bounds__(kBlock) void revert_images_kernel(VecLayout L, cons
 //                          schur_explicit(), schur_symbolic_stale, schur_symbolic, schur_eblk,
 //                          schur_assemble, schur_spmv, schur_matrix_shape, schur_matrix_copy,
 //                          schur_explicit_key
+//   HasNormal              normal(); normal_symbolic_stale, normal_symbolic, normal_eblk,
+//                          normal_assemble, normal_spmv, normal_matrix_shape, normal_matrix_copy,
+//                          normal_key
 // A trait looks for its first method by NAME only (none of these is overloaded or a
 // template): an Op whose signature drifts fails to compile where the driver calls it,
 // instead of losing the feature without a word. Each Op's source asserts the traits it
@@ -196,6 +199,14 @@ OPTAMD_OP_TRAIT(HasBlockPre, block_pre);
 // of p = 0 give the reduced right-hand side b_r - E M^-1 b_e; after it schur_back writes
 // delta_e = M^-1 (b_e - E^T delta_r), and the update, model cost and cost see the full delta.
 OPTAMD_OP_TRAIT(HasSchur, schur);
+
+// Ops that can form H = J^T J explicitly (GenericOp for NormalMatrix("explicit")): normal() says
+// whether this energy asked for it (then block_pre() holds too, and schur() does not). Once per
+// Step, after jtf has left the diagonal blocks in the block buffer and before block_init inverts
+// them, normal_symbolic (host, only after a re-wiring), normal_eblk and normal_assemble build H
+// in block-CSR; every apply of the PCG loop — and the residual reset's, and apply_jtj's — is then
+// normal_spmv, with apply's contract. LM's diagonal is not part of H: the SpMV adds dadd p.
+OPTAMD_OP_TRAIT(HasNormal, normal);
 #undef OPTAMD_OP_TRAIT
 
 // r -= Ap (and b = r, LM): the reduced right-hand side from Ap = E M^-1 b_e
@@ -305,6 +316,7 @@ public:
         linear_init(rz(0), true);   // PCGInit1 (+ LM diagonal)
         if (lm_) OPT_HIP_CHECK(hipMemsetAsync(red_.scalars + kScQ0, 0, sizeof(double), stream_));
         schur_prepare(true);   // (delta_ = 0 here: the p of the reduced right-hand side's apply)
+        normal_prepare();
         if constexpr (HasBlockPre<Op>::value)
             if (block_) {   // M_e^-1 in place of the blocks, z_0 = M^-1 r, p_0 = z_0, rz_0
                 tbegin("blk_init");
@@ -429,6 +441,8 @@ public:
         if (schur_) key.push_back((unsigned long long)(uintptr_t)w_);
         if constexpr (HasSchur<Op>::value)
             if (explicit_) op_->schur_explicit_key(&key);
+        if constexpr (HasNormal<Op>::value)
+            if (normal_) op_->normal_key(&key);
         if constexpr (!HasCaptureKey<Op>::value) {
             for (const DeclImage& im : spec_.images)   // arrays by address, scalars by value (below)
                 if (im.index >= 0 && im.index < spec_.n_params_total)
@@ -607,6 +621,31 @@ public:
         }
         return Plan::reduced_matrix(params, rowPtr, colInd, val);
     }
+    bool normal_matrix_shape(long long* rows, int* dim, long long* nnzb) const override {
+        if constexpr (HasNormal<Op>::value)
+            if (normal_) return op_->normal_matrix_shape(rows, dim, nnzb);
+        return Plan::normal_matrix_shape(rows, dim, nnzb);
+    }
+    // H at the current unknowns: bind, J^T F with its diagonal blocks, the numeric phase, then
+    // the block-CSR copied out; every buffer this writes is rebuilt by the next step
+    int normal_matrix(void** params, int* rowPtr, int* colInd, void* val) override {
+        if constexpr (HasNormal<Op>::value) {
+            if (!normal_) return 1;
+            begin_call();
+            if (!rowPtr) {   // bind + pattern only
+                op_->bind(params, stream_);
+                normal_symbolic();
+            } else {
+                prepare(params);
+                op_->jtf(r_, diag_, flags_, stream_);
+                normal_prepare();
+                op_->normal_matrix_copy(rowPtr, colInd, (T*)val, stream_);
+            }
+            end_call();
+            return 0;
+        }
+        return Plan::normal_matrix(params, rowPtr, colInd, val);
+    }
     int preconditioner_blocks(int max_images, int* group, int* first_row) const override {
         if constexpr (HasBlockPre<Op>::value)
             if (block_) return op_->block_layout(max_images, group, first_row);
@@ -621,6 +660,9 @@ public:
         if (mat_) {
             materialize();
             mat_apply((const T*)p, (T*)Ap, nullptr, kScTmp);
+        } else if (normal_) {   // the explicit path: H from this call's blocks, then the SpMV
+            normal_prepare();
+            normal_apply((const T*)p, (T*)Ap, nullptr, nullptr, red_.slot(nb(), kScTmp));
         } else {
             tbegin(Op::kApplyName);   // the same timer entry as the PCG loop's applies
             op_->apply((const T*)p, (T*)Ap, nullptr, nullptr, red_.slot(nb(), kScTmp), stream_);
@@ -741,6 +783,7 @@ private:
                 explicit_ = op_->schur_explicit();
             }
         }
+        if constexpr (HasNormal<Op>::value) normal_ = op_->normal();
         flags_ = (uint8_t*)dmalloc(dom_.npix_mem());
         OPT_HIP_CHECK(hipMemset(flags_, 0, dom_.npix_mem()));
         red_.ensure(std::max(op_->stencil_blocks(), 4096), 2, 64);
@@ -811,6 +854,37 @@ private:
                 op_->schur_symbolic(stream_);
                 tend();
             }
+    }
+
+    // NormalMatrix("explicit") plans: the pattern of H for the graphs as bound (host; a no-op
+    // while the wiring stands). A rebuild moves the SpMV's buffers, so no captured loop survives.
+    void normal_symbolic() {
+        if constexpr (HasNormal<Op>::value)
+            if (normal_ && op_->normal_symbolic_stale()) {
+                drop_graph();
+                tbegin("normal_symbolic");
+                op_->normal_symbolic(stream_);
+                tend();
+            }
+    }
+    // ... after jtf and before block_init: H itself from the diagonal blocks in blk_
+    void normal_prepare() {
+        if constexpr (HasNormal<Op>::value)
+            if (normal_) {
+                normal_symbolic();
+                tbegin("normal_eblk"); op_->normal_eblk(stream_); tend();
+                tbegin("normal_assemble"); op_->normal_assemble(stream_); tend();
+            }
+    }
+    // Ap = H p (+ dadd p) by the block SpMV; false on any other plan
+    bool normal_apply(const T* p, T* Ap, const T* dadd, const int* stop, ReduceSlot rs) {
+        if constexpr (HasNormal<Op>::value)
+            if (normal_) {
+                tbegin("normal_spmv"); op_->normal_spmv(p, Ap, dadd, stop, rs, stream_); tend();
+                return true;
+            }
+        (void)p; (void)Ap; (void)dadd; (void)stop; (void)rs;
+        return false;
     }
 
     // Schur plans, after the scalar init kernel and before block_init: M_e^-1 in place of the
@@ -916,6 +990,7 @@ private:
             }
         }
         if (schur_apply(p_, Ap_, dadd, stop, rs)) return;
+        if (normal_apply(p_, Ap_, dadd, stop, rs)) return;
         tbegin(Op::kApplyName);
         op_->apply(p_, Ap_, dadd, stop, rs, stream_);
         tend();
@@ -984,7 +1059,8 @@ private:
     }
     void pcg_reset_apply(const int* stop) {
         exchange_vec(delta_);
-        if (!schur_apply(delta_, Adelta_, CtC_, stop, red_.slot(nb(), kScTmp)))
+        if (!schur_apply(delta_, Adelta_, CtC_, stop, red_.slot(nb(), kScTmp)) &&
+            !normal_apply(delta_, Adelta_, CtC_, stop, red_.slot(nb(), kScTmp)))
             op_->apply(delta_, Adelta_, CtC_, stop, red_.slot(nb(), kScTmp), stream_);
     }
     void pcg_half2(int i, const int* stop, const ZetaArgs& z) {
@@ -1162,6 +1238,7 @@ private:
     bool schur_ = false;                       // Eliminate: PCG on the Schur complement (HasSchur)
     T *w_ = nullptr, *be_ = nullptr;           // compact (eliminated elements): M^-1-sized products, the stash of b_e
     bool explicit_ = false;                    // ReducedSystem("explicit"): S assembled per step, the apply a block SpMV
+    bool normal_ = false;                      // NormalMatrix("explicit"): H assembled per step, the apply a block SpMV (HasNormal)
     uint8_t* flags_ = nullptr;
     int* stop_ = nullptr;
     hipGraphExec_t graph_exec_ = nullptr;      // captured PCG loop (pcg_graph_begin)

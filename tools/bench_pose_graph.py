@@ -9,6 +9,16 @@ gen_apply and the constraints' gen_apply_graph together), `jtf` one J^T F with t
 preconditioner (gen_jtf and gen_jtf_graph together).
 
   python tools/bench_pose_graph.py [--side 1000] [--iters 10] [--reps 5] [--out FILE]
+
+--variants scalar,block,explicit instead runs, in one process and interleaved, the shipped file,
+its UsePreconditioner("block") variant and energies/normal_matrix/pose_graph_2d_explicit.t
+(NormalMatrix("explicit")) on the same inputs: the GN step in ms (median of --reps after a
+warm-up), then in a pass of its own the plan's per-kernel timer — the apply in us per PCG
+iteration (`normal_spmv` for the explicit form, `gen_apply` for the others), `normal_eblk` and
+`normal_assemble` per step — the host symbolic phase in ms, the shape and bytes of H, the SpMV's
+bytes (values, column indices, row pointers, p gathered once per block, Ap) over its time against
+the 6.29 TB/s float4 copy rate, and the cost after each of 5 GN steps. A library from before the
+statement (OPT_AMD_LIB) knows only scalar and block.
 """
 import argparse
 import json
@@ -49,13 +59,107 @@ def grid_world(S, seed=1):
     return V, (np.stack([i, j], 1), z, info), [0]
 
 
+def run_variants(a):
+    import tempfile
+    V, edges, fixed = grid_world(a.side)
+    w, dims = problems.pose_graph_2d(V, edges, fixed, w_anchor=10.0)
+    del V, edges
+    shipped = os.path.join(ROOT, "energies", "pose_graph_2d.t")
+    text = open(shipped).read()
+    assert "UsePreconditioner(true)" in text
+    block = os.path.join(tempfile.mkdtemp(), "pose_graph_2d_block.t")
+    open(block, "w").write(text.replace("UsePreconditioner(true)", 'UsePreconditioner("block")'))
+    files = {"scalar": shipped, "block": block,
+             "explicit": os.path.join(ROOT, "energies", "normal_matrix", "pose_graph_2d_explicit.t")}
+    names = [v for v in a.variants.split(",") if v]
+    cuda = lambda x: torch.from_numpy(x).cuda()  # noqa: E731
+    consts = problems.pose_graph_2d_params(w, cuda)
+
+    def fresh():
+        return [consts[0], consts[1].clone()] + consts[2:]
+
+    solvers = {}
+    for name in names:
+        s = OptSolver(dims, files[name], "gaussNewtonGPU")
+        assert s.family() == "generic"
+        s.set_solver_params({"nIterations": a.steps, "lIterations": a.iters})
+        solvers[name] = s
+
+    def one_step(s):
+        s.init(fresh())
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        s.step()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+
+    out = {"library": os.environ.get("OPT_AMD_LIB", "in-tree"), "poses": dims[0], "constraints": dims[1],
+           "pcg_iterations": a.iters, "precision": "fp32", "solver": "gaussNewtonGPU",
+           "device": torch.cuda.get_device_name(0)}
+    for s in solvers.values():   # warm-up: code objects, incidence lists, the pattern
+        one_step(s)
+    times = {k: [] for k in solvers}
+    for _ in range(a.reps):      # interleaved
+        for k, s in solvers.items():
+            times[k].append(one_step(s))
+    for k, s in solvers.items():
+        out[k] = {"step_ms": sorted(times[k]), "step_ms_median": float(np.median(times[k])),
+                  "cost_after_steps": s.profiled_solve(fresh())}
+    # the kernel table, in a pass of its own (event pairs around every launch slow the step)
+    for k, s in solvers.items():
+        s.set_kernel_timing(1)
+        for _ in range(3):
+            one_step(s)
+        table = {}
+        for n in ("jtf", "gn_init", "blk_init", "step2", "blk_step2", "step3", "gen_apply", "normal_eblk", "normal_assemble",
+                  "normal_spmv", "update", "cost"):
+            cnt, ms = s.kernel_stat(n)
+            if cnt:
+                table[n] = {"launches": cnt, "us_per_launch": 1e3 * ms / cnt}
+        s.set_kernel_timing(0)
+        out[k]["kernels"] = table
+        out[k]["apply_us_per_iteration"] = table.get("normal_spmv" if k == "explicit" else "gen_apply", {}).get("us_per_launch", 0.0)
+    if "explicit" in solvers:
+        # the symbolic phase alone: a fresh plan, its incidence lists built by a cost evaluation
+        # first, then the bind-and-pattern call (OptAMD_NormalMatrix without arrays)
+        from opt_amd.api import ParamPack
+        s2 = OptSolver(dims, files["explicit"], "gaussNewtonGPU")
+        prm = fresh()
+        s2.eval_cost(prm)
+        pk = ParamPack(prm)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        rc = s2.lib.OptAMD_NormalMatrix(s2.plan, pk.ptr, None, None, None)
+        ms = (time.perf_counter() - t0) * 1e3
+        assert rc == 0
+        rows, dim, nnzb = s2.normal_matrix_shape()
+        e = out["explicit"]
+        e["symbolic_build_ms"] = ms
+        e["block_rows"], e["block_dim"], e["blocks"] = rows, dim, nnzb
+        e["matrix_bytes"] = nnzb * dim * dim * 4
+        # what one SpMV moves: values, column indices, row pointers, p once per block, Ap and p once per row
+        e["spmv_bytes"] = nnzb * dim * dim * 4 + nnzb * 4 + (rows + 1) * 4 + nnzb * dim * 4 + 2 * rows * dim * 4
+        spmv = e["kernels"].get("normal_spmv", {}).get("us_per_launch", 0.0)
+        e["spmv_TB_per_s"] = e["spmv_bytes"] / (spmv * 1e-6) / 1e12 if spmv else 0.0
+        e["spmv_over_copy_rate"] = e["spmv_TB_per_s"] / 6.29   # the float4 copy rate measured on this chip
+        s2.close()
+    print(json.dumps(out))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        open(a.out, "w").write(json.dumps(out, indent=1) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--side", type=int, default=1000)
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--variants", default="")
     ap.add_argument("--out")
     a = ap.parse_args()
+    if a.variants:
+        return run_variants(a)
     V, edges, fixed = grid_world(a.side)
     w, dims = problems.pose_graph_2d(V, edges, fixed, w_anchor=10.0)
     del V, edges
