@@ -195,6 +195,14 @@ int OptAMD_KernelStat(Opt_Plan* plan, const char* name, long long* launches, dou
  * rocprofv3 kernel traces. */
 int OptAMD_ApplyKernelName(Opt_Plan* plan, char* buf, int buflen);
 
+/* Which forms of the generated kernels this plan launches, after the OPT_AMD_GEN_APPLY / _JTF /
+ * _COST knobs, the wave-count rule, row slabs and the block preconditioner, as one line of
+ * key=value words: "apply=gather|tiled|strip jtf=gather|strip cost=gather|strip grid=<blocks>
+ * rows=<image rows> apply_row_block=<rows> jtf_row_block=<rows> cost_row_block=<rows>
+ * materialized=0|1" (a strip form walks blocks of that many rows per wave; 0 for the other
+ * forms). Returns the length, or -1 on a plan that is not on generated kernels. */
+int OptAMD_PlanGeneratedForms(Opt_Plan* plan, char* buf, int buflen);
+
 /* Human-readable table of every timed kernel (reference timer report,
  * backend_cuda.t:231-297). Returns the length written. */
 int OptAMD_KernelReport(Opt_Plan* plan, char* buf, int buflen);
@@ -318,6 +326,13 @@ int OptAMD_GenericPlanCheck(const char* filename, char* buf, int n);
  * toenergyspecs / classifyexpression result, API/src/o.t:2669-2715). Returns the residual
  * count, or -1 with the front end's message in buf. */
 int OptAMD_GenericDescribe(const char* filename, char* buf, int n);
+
+/* What the generator emitted for `filename` beside the gathers, as one line of key=value
+ * words: "has_tiled tiles_x tiles_y has_strip strip_cols has_jtf_strip jtf_strip_cols
+ * has_cost_strip cost_strip_cols" (a form that cannot serve the energy, or whose row windows
+ * pass the register cap, is not emitted, and a plan then keeps the gather). Returns the
+ * length, or -1 with the front end's message in buf. No device needed. */
+int OptAMD_GenericForms(const char* filename, int doublePrecision, char* buf, int n);
 
 /* Compile that source for gfx950 with hiprtc (no device needed). 0 on success, -1 with
  * the compiler log (or the front end's message) in buf. */

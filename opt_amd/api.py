@@ -70,6 +70,7 @@ _SIGNATURES = [
     ("OptAMD_SetKernelTiming", None, [_VP, ctypes.c_int]),
     ("OptAMD_KernelStat", ctypes.c_int, [_VP, ctypes.c_char_p, ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_double)]),
     ("OptAMD_ApplyKernelName", ctypes.c_int, [_VP, ctypes.c_char_p, ctypes.c_int]),
+    ("OptAMD_PlanGeneratedForms", ctypes.c_int, [_VP, ctypes.c_char_p, ctypes.c_int]),
     ("OptAMD_KernelReport", ctypes.c_int, [_VP, ctypes.c_char_p, ctypes.c_int]),
     ("OptAMD_PlanStream", _VP, [_VP]),
     ("OptAMD_PlanIterations", ctypes.c_int, [_VP]),
@@ -114,6 +115,7 @@ _SIGNATURES = [
                                             ctypes.POINTER(ctypes.c_longlong), _VP, _VP, _VP, _VP, ctypes.c_char_p,
                                             ctypes.c_int]),
     ("OptAMD_GenericCompileCheck", ctypes.c_int, [ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]),
+    ("OptAMD_GenericForms", ctypes.c_int, [ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]),
 ]
 EXPORTED_SYMBOLS = [s[0] for s in _SIGNATURES]
 
@@ -421,6 +423,15 @@ class OptSolver:
         self.lib.OptAMD_ApplyKernelName(self.plan, buf, 64)
         return buf.value.decode()
 
+    def generated_forms(self) -> dict:
+        """Which forms of the generated kernels this plan launches (OptAMD_PlanGeneratedForms):
+        'apply' / 'jtf' / 'cost' as strings, the grid, the image rows and the strips' row-block
+        lengths as ints. OptError on a plan that is not on generated kernels."""
+        buf = ctypes.create_string_buffer(512)
+        if self.lib.OptAMD_PlanGeneratedForms(self.plan, buf, 512) < 0:
+            raise OptError("OptAMD_PlanGeneratedForms: the plan is not on generated kernels")
+        return _words(buf.value.decode())
+
     def kernel_report(self) -> str:
         buf = ctypes.create_string_buffer(1 << 16)
         self.lib.OptAMD_KernelReport(self.plan, buf, 1 << 16)
@@ -541,6 +552,25 @@ def generic_source(energy_file: str, double: bool = False, off32: bool = False) 
     if r < 0:
         raise OptError(txt)
     return txt
+
+
+def _words(line: str) -> dict:
+    """'key=value' words of one report line: integers as int, the rest as str."""
+    out = {}
+    for w in line.split():
+        k, v = w.split("=", 1)
+        out[k] = int(v) if v.lstrip("-").isdigit() else v
+    return out
+
+
+def generic_forms(energy_file: str, double: bool = False) -> dict:
+    """What the generator emits for `energy_file` beside the gathers (OptAMD_GenericForms):
+    has_tiled, tiles_x, tiles_y, has_strip, strip_cols, has_jtf_strip, jtf_strip_cols,
+    has_cost_strip, cost_strip_cols, all ints. No device needed."""
+    r, txt = _text_call(load_library().OptAMD_GenericForms, energy_file.encode(), int(double), cap=512)
+    if r < 0:
+        raise OptError(txt)
+    return _words(txt)
 
 
 def generic_describe(energy_file: str) -> List[str]:

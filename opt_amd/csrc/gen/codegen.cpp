@@ -131,7 +131,20 @@ void emit_prelude(const Ctx& cx, std::ostringstream& o) {
          "__device__ __forceinline__ void opt_sincos(double x, double* s, double* c) { sincos(x, s, c); }\n";
     // whole-wave DPP lane shifts (wave_shl:1 / wave_shr:1): opt_sh(v, d) is v of lane l + d
     // (0 past the wave's ends); d is a literal at every use, so the loops unroll away
-    // (bound_ctrl: the hardware shifts 0 into the end lane, no register set to 0 first)
+    // (bound_ctrl: the hardware shifts 0 into the end lane, no register set to 0 first).
+    // An energy that reads further than one column away chains shifts (|d| > 1), and its
+    // loops carry `#pragma unroll`: left to the optimizer's own unroller after inlining, a
+    // kernel with several chained shifts (gen_jtf_strip of an energy with offsets (2,-1) and
+    // (-2,3), in float) crashed the compiler inside hiprtcCompileProgram. Radius-1 energies
+    // keep the plain loops, and with them their source byte for byte.
+    bool wide = false;
+    {
+        std::vector<int> roots;
+        for (auto& r : m.residuals) roots.push_back(r.expr);
+        for (auto& x : m.excludes) roots.push_back(x.second);
+        for (int e : roots)
+            m.pool.visit(e, [&](int, const Node& n) { wide = wide || (n.op == Op::Read && n.slot < 0 && std::abs(n.off[0]) > 1); });
+    }
     o << "__device__ __forceinline__ float opt_lr(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x130, 0xf, 0xf, true)); }\n"
          "__device__ __forceinline__ float opt_ll(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x138, 0xf, 0xf, true)); }\n"
          "__device__ __forceinline__ double opt_dd(double v, bool r) {\n"
@@ -140,8 +153,14 @@ void emit_prelude(const Ctx& cx, std::ostringstream& o) {
          "    const int hi = r ? __builtin_amdgcn_update_dpp(0, (int)(b >> 32), 0x130, 0xf, 0xf, true) : __builtin_amdgcn_update_dpp(0, (int)(b >> 32), 0x138, 0xf, 0xf, true);\n"
          "    return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);\n}\n"
          "__device__ __forceinline__ double opt_lr(double v) { return opt_dd(v, true); }\n"
-         "__device__ __forceinline__ double opt_ll(double v) { return opt_dd(v, false); }\n"
-         "__device__ __forceinline__ T opt_sh(T v, int d) { for (; d > 0; --d) v = opt_lr(v); for (; d < 0; ++d) v = opt_ll(v); return v; }\n";
+         "__device__ __forceinline__ double opt_ll(double v) { return opt_dd(v, false); }\n";
+    if (wide)
+        o << "__device__ __forceinline__ T opt_sh(T v, int d) {\n"
+             "    _Pragma(\"unroll\") for (; d > 0; --d) v = opt_lr(v);\n"
+             "    _Pragma(\"unroll\") for (; d < 0; ++d) v = opt_ll(v);\n"
+             "    return v;\n}\n";
+    else
+        o << "__device__ __forceinline__ T opt_sh(T v, int d) { for (; d > 0; --d) v = opt_lr(v); for (; d < 0; ++d) v = opt_ll(v); return v; }\n";
     // masked read without a branch: the load always issues (at element 0 of the array when
     // the access is outside), the value is selected afterwards
     // XCD-contiguous block order for the graph kernels and the register strips: the

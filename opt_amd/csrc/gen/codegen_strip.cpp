@@ -348,10 +348,18 @@ void emit_scatter_strip(Ctx& cx, std::ostringstream& o, bool jtf) {
     auto at = [&](const std::string& arr, const std::string& e) {
         return s32 ? std::string(rw.opq ? "opt_at32<true>(" : "opt_at32<false>(") + arr + ", " + e + ")" : arr + "[" + e + "]";
     };
+    // An Exclude that reads at a column offset takes its value from a neighbouring lane (a DPP
+    // shift), and a shift reads 0 from a lane that is switched off: inside the branch on xout
+    // the halo lanes are, so the first output column of every strip but the leftmost saw its
+    // left neighbour's mask as 0 and was never excluded. Such a test is evaluated before the
+    // branch, by the whole wave (a test at the centre column stays where it was).
+    const bool hoist = jtf && fin.str().find("opt_sh(") != std::string::npos;
+    if (hoist) o << "        bool act_o;\n        {\n" << fin.str() << "        act_o = act;\n        }\n";
     o << "        const int yo = y + " << miny << ";\n"
          "        if (xout && yo >= y0 && yo < y1) {\n"
          "        const " << ity << " lin = (" << ity << ")yo * W + x;\n";
-    if (jtf) o << fin.str() << "        " << at("a.flags", "lin") << " = act ? 1 : 0;\n";
+    if (hoist) o << "        const bool act = act_o;\n        " << at("a.flags", "lin") << " = act ? 1 : 0;\n";
+    else if (jtf) o << fin.str() << "        " << at("a.flags", "lin") << " = act ? 1 : 0;\n";
     else o << "        const bool act = (" << at("a.flags", "lin") << " & 1) != 0;\n";
     for (int k : unk)
         for (int c = 0; c < m.images[k].channels; ++c) {

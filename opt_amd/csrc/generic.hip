@@ -795,6 +795,23 @@ public:
     // the graphs' vertex arrays changed (check_graphs; stencil_plan.h, HasTopologyGeneration)
     unsigned long long topology_generation() const { return topology_generation_; }
 
+    // The forms load_module chose (OptAMD_PlanGeneratedForms; StencilPlan: HasGeneratedForms), the
+    // grid every generated kernel is launched with, and per strip form the rows a wave walks:
+    // the strips' own rule (codegen_strip.cpp open_waves) for this grid of 4-wave blocks.
+    std::string generated_forms() const {
+        const int grid = stencil_blocks(), H = dims_[1];
+        auto row_block = [&](const char* form, int cols) {
+            if (std::string(form) != "strip") return 0;
+            const long long nsx = (dims_[0] + cols - 1) / cols, G = 4LL * grid;
+            return (int)std::max<long long>(8, ((long long)H * nsx + G - 1) / G);
+        };
+        char line[256];
+        snprintf(line, sizeof line, "apply=%s jtf=%s cost=%s grid=%d rows=%d apply_row_block=%d jtf_row_block=%d cost_row_block=%d",
+                 apply_form_, jtf_form_, cost_form_, grid, H, row_block(apply_form_, src_.strip_cols),
+                 row_block(jtf_form_, src_.jtf_strip_cols), row_block(cost_form_, src_.cost_strip_cols));
+        return line;
+    }
+
     const std::string& source() const { return src_.code; }
     bool tiled_selected() const { return k_apply_ == k_apply_tiled_; }
 
@@ -866,7 +883,7 @@ private:
         const std::string force = want ? want : "";
         if (src_.has_tiled && !slab) {
             OPT_HIP_CHECK(hipModuleGetFunction(&k_apply_tiled_, mod_, "gen_apply_tiled"));
-            if (force == "tiled" || (force.empty() && src_.prefer_tiled)) k_apply_ = k_apply_tiled_;
+            if (force == "tiled" || (force.empty() && src_.prefer_tiled)) { k_apply_ = k_apply_tiled_; apply_form_ = "tiled"; }
         }
         if (src_.has_strip && !slab) {
             // one wave per (column strip, >= 8-row block): a small image leaves most SIMDs
@@ -874,7 +891,7 @@ private:
             // the other forms run
             OPT_HIP_CHECK(hipModuleGetFunction(&k_apply_strip_, mod_, "gen_apply_strip"));
             const long long waves = (long long)((dims_[0] + src_.strip_cols - 1) / src_.strip_cols) * ((dims_[1] + 7) / 8);
-            if (force == "strip" || (force.empty() && waves >= 2048)) k_apply_ = k_apply_strip_;
+            if (force == "strip" || (force.empty() && waves >= 2048)) { k_apply_ = k_apply_strip_; apply_form_ = "strip"; }
         }
         // Strip waves walk whole row blocks, so a grid of 1.33 resident rounds leaves a third
         // of the chip idle in its tail: with the strip apply, launch exactly the blocks that
@@ -916,16 +933,20 @@ private:
             const char* wj = getenv("OPT_AMD_GEN_JTF");
             const std::string fj = wj ? wj : "";
             const long long waves = (long long)((dims_[0] + src_.jtf_strip_cols - 1) / src_.jtf_strip_cols) * ((dims_[1] + 7) / 8);
-            if (fj == "strip" || (fj.empty() && waves >= 2048))
+            if (fj == "strip" || (fj.empty() && waves >= 2048)) {
                 OPT_HIP_CHECK(hipModuleGetFunction(&k_jtf_, mod_, "gen_jtf_strip"));
+                jtf_form_ = "strip";
+            }
         }
         // cost / model cost: the register strip under the same rule (OPT_AMD_GEN_COST forces)
         if (src_.has_cost_strip && !slab) {
             const char* wc = getenv("OPT_AMD_GEN_COST");
             const std::string fc = wc ? wc : "";
             const long long waves = (long long)((dims_[0] + src_.cost_strip_cols - 1) / src_.cost_strip_cols) * ((dims_[1] + 7) / 8);
-            if (fc == "strip" || (fc.empty() && waves >= 2048))
+            if (fc == "strip" || (fc.empty() && waves >= 2048)) {
                 OPT_HIP_CHECK(hipModuleGetFunction(&k_cost_, mod_, "gen_cost_strip"));
+                cost_form_ = "strip";
+            }
         }
         k_dump_.resize(src_.dump.size());
         for (size_t k = 0; k < src_.dump.size(); ++k)
@@ -1061,6 +1082,7 @@ private:
     hipModule_t mod_ = nullptr;
     std::vector<hipFunction_t> k_pre_, k_dump_;
     hipFunction_t k_apply_tiled_{}, k_apply_strip_{};
+    const char *apply_form_ = "gather", *jtf_form_ = "gather", *cost_form_ = "gather";   // what load_module chose
     hipFunction_t k_jtf_{}, k_apply_{}, k_cost_{}, k_jtf_graph_{}, k_apply_graph_{};
     hipFunction_t k_blk_init_{}, k_blk_step2_{}, k_blk_half2_{}, k_blk_apply_{};
     std::vector<gen::GBlockGroup> groups_;   // block preconditioner: empty without it
@@ -1091,6 +1113,7 @@ static_assert(HasRefreshCaches<GenericOp<float>>::value);
 static_assert(HasSlabRefusal<GenericOp<float>>::value);
 static_assert(HasTopologyGeneration<GenericOp<float>>::value);
 static_assert(HasDumpJ<GenericOp<float>>::value);
+static_assert(HasGeneratedForms<GenericOp<float>>::value);
 
 std::unique_ptr<Plan> make_generic_plan(const ProblemSpec& spec, const StateOptions& opts, const unsigned* dims,
                                         std::string* err) {
@@ -1174,6 +1197,24 @@ int generic_source(const std::string& text, bool dbl, std::string* out, bool off
     if (!gen::build_model(text, &m, &err)) { *out = err; return -1; }
     if (!m.unsupported.empty()) { *out = "unsupported: " + m.unsupported; return -1; }
     *out = gen::generate(m, dbl, off32).code;
+    return (int)out->size();
+}
+
+// What generate() emitted beside the gathers (tests / inspection; tools/gen_dump.cpp prints
+// the same fields).
+int generic_forms(const std::string& text, bool dbl, std::string* out) {
+    gen::GModel m;
+    std::string err;
+    if (!gen::build_model(text, &m, &err)) { *out = err; return -1; }
+    if (!m.unsupported.empty()) { *out = "unsupported: " + m.unsupported; return -1; }
+    const gen::GenSource gs = gen::generate(m, dbl);
+    char line[256];
+    snprintf(line, sizeof line,
+             "has_tiled=%d tiles_x=%d tiles_y=%d has_strip=%d strip_cols=%d has_jtf_strip=%d jtf_strip_cols=%d "
+             "has_cost_strip=%d cost_strip_cols=%d",
+             (int)gs.has_tiled, gs.tiles_x, gs.tiles_y, (int)gs.has_strip, gs.strip_cols, (int)gs.has_jtf_strip,
+             gs.jtf_strip_cols, (int)gs.has_cost_strip, gs.cost_strip_cols);
+    *out = line;
     return (int)out->size();
 }
 

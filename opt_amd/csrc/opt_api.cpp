@@ -318,6 +318,12 @@ int OptAMD_ApplyKernelName(Opt_Plan* plan, char* buf, int n) {
     return valid_plan(plan, "OptAMD_ApplyKernelName") ? copy_name(plan->impl->apply_kernel_name(), buf, n)
                                                       : -1;
 }
+int OptAMD_PlanGeneratedForms(Opt_Plan* plan, char* buf, int n) {
+    if (!valid_plan(plan, "OptAMD_PlanGeneratedForms")) return -1;
+    std::string s;
+    if (plan->impl->generated_forms(&s) < 0) return -1;
+    return copy_name(s, buf, n);
+}
 int OptAMD_KernelReport(Opt_Plan* plan, char* buf, int n) {
     return valid_plan(plan, "OptAMD_KernelReport") ? copy_name(plan->impl->timer().report(), buf, n) : -1;
 }
@@ -494,6 +500,13 @@ int OptAMD_GenericSource(const char* filename, int doublePrecision, char* buf, i
     std::string text, out;
     if (!read_file(filename, &text)) return copy_name("cannot read energy file", buf, n), -1;
     const int r = optamd::generic_source(text, (doublePrecision & 1) != 0, &out, (doublePrecision & 2) != 0);
+    copy_name(out, buf, n);
+    return r;
+}
+int OptAMD_GenericForms(const char* filename, int doublePrecision, char* buf, int n) {
+    std::string text, out;
+    if (!read_file(filename, &text)) return copy_name("cannot read energy file", buf, n), -1;
+    const int r = optamd::generic_forms(text, doublePrecision != 0, &out);
     copy_name(out, buf, n);
     return r;
 }

@@ -114,6 +114,9 @@ public:
     virtual double eval_cost(void** params) = 0;
     virtual double time_apply(void** params, const void* p, void* Ap, int reps) = 0;
     virtual std::string apply_kernel_name() const = 0;
+    // Which generated kernel forms this plan launches (include/opt_amd.h
+    // OptAMD_PlanGeneratedForms); -1 for a plan that is not on generated kernels.
+    virtual int generated_forms(std::string* out) const { (void)out; return -1; }
     // Row-slab decomposition (image domains): this rank owns global rows [y_lo, y_hi)
     // and the caller's arrays hold rows [y_lo - halo_lo, y_hi + halo_hi) with
     // halo_lo = min(halo, y_lo), halo_hi = min(halo, H - y_hi). Returns an error text

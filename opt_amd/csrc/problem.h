@@ -69,6 +69,9 @@ bool classify(ProblemSpec* spec, std::string* err);
 bool generic_accepts(const std::string& text, ProblemSpec* spec, std::string* err);
 int generic_source(const std::string& text, bool dbl, std::string* out, bool off32 = false);
 int generic_describe(const std::string& text, std::string* out);
+// What generate() emitted for the energy beside the gathers, as one line of key=value words
+// (GenSource's has_* / tiles / *_cols fields); -1 + message if the energy does not lower.
+int generic_forms(const std::string& text, bool dbl, std::string* out);
 int generic_compile_check(const std::string& text, bool dbl, std::string* log);
 // The shape checks Opt_ProblemPlan runs on the lowered energy before it asks for a device
 // (ReducedSystem("explicit")'s accepted shapes): 0 accepted, 1 refused + the plan's message,

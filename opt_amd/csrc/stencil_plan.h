@@ -207,6 +207,10 @@ OPTAMD_OP_TRAIT(HasSchur, schur);
 // in block-CSR; every apply of the PCG loop — and the residual reset's, and apply_jtj's — is then
 // normal_spmv, with apply's contract. LM's diagonal is not part of H: the SpMV adds dadd p.
 OPTAMD_OP_TRAIT(HasNormal, normal);
+
+// Ops that choose among several forms of their kernels (GenericOp: gather, LDS tiles, register
+// strips): std::string generated_forms() const, the forms this plan launches.
+OPTAMD_OP_TRAIT(HasGeneratedForms, generated_forms);
 #undef OPTAMD_OP_TRAIT
 
 // r -= Ap (and b = r, LM): the reduced right-hand side from Ap = E M^-1 b_e
@@ -248,6 +252,14 @@ public:
     long long unknown_count() const override { return n_; }
     std::string family() const override { return Op::kName; }
     std::string apply_kernel_name() const override { return mat_ ? mat_->apply_name() : Op::kApplyName; }
+    int generated_forms(std::string* out) const override {
+        if constexpr (HasGeneratedForms<Op>::value) {
+            // (a materialized plan's applies are SpMVs of the dumped J, not the apply form named here)
+            *out = op_->generated_forms() + (mat_ ? " materialized=1" : " materialized=0");
+            return 0;
+        }
+        return -1;
+    }
     int halo() const override { return op_->halo(); }
     int unknown_layout(int max_images, long long* offset, long long* elements, int* channels) const override {
         for (int k = 0; k < L_.nimg && k < max_images; ++k) {

@@ -287,12 +287,13 @@ def test_refusals_name_their_cause(capfd):
 
 
 # ---------------------------------------------------------------------------- row bias
-def solve_with_excluded_centres(model, cost_rows, active, n_iter, l_iter, lm):
+def solve_with_excluded_centres(model, cost_rows, active, n_iter, l_iter, lm, use_pre=False):
     """The C oracle's GN / LM loop (oracle_solve_f64, as examples_ad.solve drives it) with
     the reference's Exclude rule, which examples_ad.solve does not have: cost and model cost
     sum only the rows `cost_rows`; r = -J^T F and J^T J p keep every row and vanish on the
-    excluded unknowns, as the kernels write them. UsePreconditioner(false). Returns the
-    costs after init and after each step."""
+    excluded unknowns, as the kernels write them. use_pre: UsePreconditioner(true), the
+    diagonal preconditioner on the active unknowns. Returns the costs after init and after
+    each step."""
     import ctypes
     lib = ad._c.load()
     lib.oracle_solve_f64.restype = ctypes.c_int
@@ -335,7 +336,7 @@ def solve_with_excluded_centres(model, cost_rows, active, n_iter, l_iter, lm):
 
     cbs = [ad._COST(cost), ad._JTF(jtf), ad._APPLY(apply), ad._MODEL(model_cost), ad._UPD(update),
            ad._VOID(save), ad._VOID(revert)]
-    P = ad._Problem(n, act.ctypes.data, 0, None, *cbs, None, None)
+    P = ad._Problem(n, act.ctypes.data, int(use_pre), None, *cbs, None, None)
     sp = ad.default_params(n_iter, l_iter)
     costs = np.zeros(n_iter + 1)
     k = lib.oracle_solve_f64(ctypes.byref(P), int(lm), ctypes.byref(sp), costs.ctypes.data_as(ad._D))
