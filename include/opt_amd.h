@@ -133,6 +133,24 @@ int OptAMD_SchurPattern(long long nEliminated, long long nRetained, int nLists, 
                         const int* const* retVertex, const long long* nEdges, long long* counts, int* rowPtr,
                         int* colInd, int* pairPtr, int* pairs, char* buf, int buflen);
 
+/* The same symbolic phase run by the device builder a plan uses (sorts and scans on the current
+ * device's null stream): host arrays in, host arrays out, the index check on the host as above,
+ * every array equal to OptAMD_SchurPattern's element for element, the refusals word for word.
+ * Needs a device but no plan and no energy file. */
+int OptAMD_SchurPatternDevice(long long nEliminated, long long nRetained, int nLists, const int* const* elimVertex,
+                              const int* const* retVertex, const long long* nEdges, long long* counts, int* rowPtr,
+                              int* colInd, int* pairPtr, int* pairs, char* buf, int buflen);
+
+/* Where the last symbolic phase of an explicit S or H ran, one line of key=value words in buf:
+ *   path=device|host reason=default|env|memory pairs=N blocks=N instances=N transient_bytes=N
+ * A plan builds the pattern on the device; OPT_AMD_SYMBOLIC=host|device, read when the plan is
+ * made, selects the path (reason=env). A wiring whose device temporaries (transient_bytes)
+ * exceed the free device memory less the buffers that stay, or OPT_AMD_SYMBOLIC_MAX_BYTES when
+ * set, takes the host path without an error (path=host reason=memory). Returns the line's
+ * length (0, an empty line, before the first symbolic phase), -1 on a plan with neither
+ * ReducedSystem("explicit") nor NormalMatrix("explicit"), or for NULL. */
+int OptAMD_PlanSymbolicInfo(Opt_Plan* plan, char* buf, int buflen);
+
 /* The explicitly formed normal matrix: NormalMatrix("explicit") in an energy file whose unknowns
  * lie over one index space makes the plan assemble H = J^T J once per Step in block-CSR (blocks
  * of blockDim x blockDim, blockDim the channels of all unknowns of one element, row-major inside
@@ -165,6 +183,11 @@ int OptAMD_NormalMatrix(Opt_Plan* plan, void** problemparams, int* rowPtr, int* 
 int OptAMD_NormalPattern(long long nVertices, int nLists, const int* const* vertex, const int* listGraph,
                          const long long* graphEdges, int nGraphs, long long* counts, int* rowPtr, int* colInd,
                          int* pairPtr, int* pairs, char* buf, int buflen);
+
+/* The same on the device, as OptAMD_SchurPatternDevice is to OptAMD_SchurPattern. */
+int OptAMD_NormalPatternDevice(long long nVertices, int nLists, const int* const* vertex, const int* listGraph,
+                               const long long* graphEdges, int nGraphs, long long* counts, int* rowPtr, int* colInd,
+                               int* pairPtr, int* pairs, char* buf, int buflen);
 
 /* Ap = J^T J p at the current unknowns (+ CtC*p for LM plans, with the CtC of the
  * last LM step) and *p_dot_Ap = p.Ap (reference kernels.PCGStep1,

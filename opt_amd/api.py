@@ -107,6 +107,11 @@ _SIGNATURES = [
                                            ctypes.POINTER(_VP), ctypes.POINTER(ctypes.c_longlong),
                                            ctypes.POINTER(ctypes.c_longlong), _VP, _VP, _VP, _VP, ctypes.c_char_p,
                                            ctypes.c_int]),
+    ("OptAMD_SchurPatternDevice", ctypes.c_int, [ctypes.c_longlong, ctypes.c_longlong, ctypes.c_int, ctypes.POINTER(_VP),
+                                                 ctypes.POINTER(_VP), ctypes.POINTER(ctypes.c_longlong),
+                                                 ctypes.POINTER(ctypes.c_longlong), _VP, _VP, _VP, _VP, ctypes.c_char_p,
+                                                 ctypes.c_int]),
+    ("OptAMD_PlanSymbolicInfo", ctypes.c_int, [_VP, ctypes.c_char_p, ctypes.c_int]),
     ("OptAMD_PlanNormalMatrixShape", ctypes.c_int, [_VP, ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_int),
                                                     ctypes.POINTER(ctypes.c_longlong)]),
     ("OptAMD_NormalMatrix", ctypes.c_int, [_VP, ctypes.POINTER(_VP), _VP, _VP, _VP]),
@@ -114,6 +119,10 @@ _SIGNATURES = [
                                             ctypes.POINTER(ctypes.c_longlong), ctypes.c_int,
                                             ctypes.POINTER(ctypes.c_longlong), _VP, _VP, _VP, _VP, ctypes.c_char_p,
                                             ctypes.c_int]),
+    ("OptAMD_NormalPatternDevice", ctypes.c_int, [ctypes.c_longlong, ctypes.c_int, ctypes.POINTER(_VP),
+                                                  ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_longlong), ctypes.c_int,
+                                                  ctypes.POINTER(ctypes.c_longlong), _VP, _VP, _VP, _VP, ctypes.c_char_p,
+                                                  ctypes.c_int]),
     ("OptAMD_GenericCompileCheck", ctypes.c_int, [ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]),
     ("OptAMD_GenericForms", ctypes.c_int, [ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]),
 ]
@@ -369,6 +378,16 @@ class OptSolver:
             raise OptError("OptAMD_ReducedMatrix failed")
         return row_ptr, col_ind[:nnzb], val[:nnzb]
 
+    def symbolic_info(self):
+        """Where the last symbolic phase of the explicit S or H ran (OptAMD_PlanSymbolicInfo): one
+        line 'path=device|host reason=default|env|memory pairs= blocks= instances=
+        transient_bytes=', '' before the first symbolic phase, -1 on a plan with neither
+        ReducedSystem("explicit") nor NormalMatrix("explicit")."""
+        buf = ctypes.create_string_buffer(256)
+        if self.lib.OptAMD_PlanSymbolicInfo(self.plan, buf, 256) < 0:
+            return -1
+        return buf.value.decode()
+
     def normal_matrix_shape(self):
         """(block rows, block dimension, blocks) of the explicitly formed H = J^T J once the
         graphs are bound (OptAMD_PlanNormalMatrixShape); None on any other plan, or before."""
@@ -598,12 +617,15 @@ def generic_plan_check(energy_file: str) -> str:
     return txt if r else ""
 
 
-def schur_pattern(n_eliminated: int, n_retained: int, lists):
+def schur_pattern(n_eliminated: int, n_retained: int, lists, device: bool = False):
     """Symbolic phase of the explicitly formed Schur complement on the host
-    (OptAMD_SchurPattern). lists: (eliminated vertex per edge, retained vertex per edge) pairs.
+    (OptAMD_SchurPattern), or with device=True by the device builder a plan uses
+    (OptAMD_SchurPatternDevice: the same arrays element for element). lists: (eliminated vertex
+    per edge, retained vertex per edge) pairs.
     Returns (counts {instances, pairs, blocks}, rowPtr, colInd, pairPtr, pairs[npairs, 2])."""
     import numpy as np
     lib = load_library()
+    fn = lib.OptAMD_SchurPatternDevice if device else lib.OptAMD_SchurPattern
     ev = [np.ascontiguousarray(a, np.int32) for a, _ in lists]
     rv = [np.ascontiguousarray(b, np.int32) for _, b in lists]
     k = len(lists)
@@ -612,24 +634,26 @@ def schur_pattern(n_eliminated: int, n_retained: int, lists):
     ne = (ctypes.c_longlong * max(k, 1))(*[len(a) for a in ev])
     counts = (ctypes.c_longlong * 3)()
     buf = ctypes.create_string_buffer(512)
-    if lib.OptAMD_SchurPattern(n_eliminated, n_retained, k, evp, rvp, ne, counts, None, None, None, None, buf, 512):
+    if fn(n_eliminated, n_retained, k, evp, rvp, ne, counts, None, None, None, None, buf, 512):
         raise OptError(buf.value.decode())
     nq, npairs, nnzb = list(counts)
     row_ptr, col_ind = np.zeros(n_retained + 1, np.int32), np.zeros(nnzb, np.int32)
     pair_ptr, pairs = np.zeros(nnzb + 1, np.int32), np.zeros((npairs, 2), np.int32)
-    if lib.OptAMD_SchurPattern(n_eliminated, n_retained, k, evp, rvp, ne, counts, row_ptr.ctypes.data, col_ind.ctypes.data,
-                               pair_ptr.ctypes.data, pairs.ctypes.data, buf, 512):
+    if fn(n_eliminated, n_retained, k, evp, rvp, ne, counts, row_ptr.ctypes.data, col_ind.ctypes.data,
+          pair_ptr.ctypes.data, pairs.ctypes.data, buf, 512):
         raise OptError(buf.value.decode())
     return {"instances": nq, "pairs": npairs, "blocks": nnzb}, row_ptr, col_ind, pair_ptr, pairs
 
 
-def normal_pattern(n_vertices: int, lists, graph_edges=None):
-    """Symbolic phase of the explicitly formed J^T J on the host (OptAMD_NormalPattern). lists:
+def normal_pattern(n_vertices: int, lists, graph_edges=None, device: bool = False):
+    """Symbolic phase of the explicitly formed J^T J on the host (OptAMD_NormalPattern), or with
+    device=True by the device builder a plan uses (OptAMD_NormalPatternDevice). lists:
     one vertex array per slot over the unknowns' space, or (graph, vertex array) pairs with
     graph_edges the edge count of each graph. Returns (counts {instances, pairs, blocks},
     rowPtr, colInd, pairPtr, pairs[npairs, 2])."""
     import numpy as np
     lib = load_library()
+    fn = lib.OptAMD_NormalPatternDevice if device else lib.OptAMD_NormalPattern
     if graph_edges is None:
         lists = [(0, v) for v in lists]
         graph_edges = [len(lists[0][1])] if lists else []
@@ -640,13 +664,13 @@ def normal_pattern(n_vertices: int, lists, graph_edges=None):
     ge = (ctypes.c_longlong * max(ng, 1))(*graph_edges)
     counts = (ctypes.c_longlong * 3)()
     buf = ctypes.create_string_buffer(512)
-    if lib.OptAMD_NormalPattern(n_vertices, k, vp, lg, ge, ng, counts, None, None, None, None, buf, 512):
+    if fn(n_vertices, k, vp, lg, ge, ng, counts, None, None, None, None, buf, 512):
         raise OptError(buf.value.decode())
     nq, npairs, nnzb = list(counts)
     row_ptr, col_ind = np.zeros(n_vertices + 1, np.int32), np.zeros(nnzb, np.int32)
     pair_ptr, pairs = np.zeros(nnzb + 1, np.int32), np.zeros((npairs, 2), np.int32)
-    if lib.OptAMD_NormalPattern(n_vertices, k, vp, lg, ge, ng, counts, row_ptr.ctypes.data, col_ind.ctypes.data,
-                                pair_ptr.ctypes.data, pairs.ctypes.data, buf, 512):
+    if fn(n_vertices, k, vp, lg, ge, ng, counts, row_ptr.ctypes.data, col_ind.ctypes.data,
+          pair_ptr.ctypes.data, pairs.ctypes.data, buf, 512):
         raise OptError(buf.value.decode())
     return {"instances": nq, "pairs": npairs, "blocks": nnzb}, row_ptr, col_ind, pair_ptr, pairs
 

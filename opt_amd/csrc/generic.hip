@@ -21,6 +21,7 @@
 #include "gen/codegen.h"
 #include "graph_util.h"
 #include "schur_pattern.h"
+#include "schur_pattern_dev.h"
 #include "stencil_plan.h"
 
 namespace optamd {
@@ -557,7 +558,8 @@ public:
         launch(k_schur_apply_, s, {&a_, &p, &w_, &Ap, &dadd, &stop, &rs});
     }
     // ---- the explicitly formed S (ReducedSystem("explicit"); gen/codegen_schur_explicit.cpp) ----
-    // Symbolic phase (host, schur_pattern.h): block-CSR pattern and per-block pair lists, built
+    // Symbolic phase (device, schur_pattern_dev.hip; host, schur_pattern.h, under OPT_AMD_SYMBOLIC=host
+    // or where the device form's temporaries do not fit): block-CSR pattern and per-block pair lists, built
     // from the vertex arrays at the first use and again when the graphs were re-wired. Numeric
     // phase, once per Step between schur_rhs (M_e^-1 in blk) and block_init (which inverts B_r
     // in place): schur_eblk writes W_q, Y_q per edge instance, schur_assemble sums the blocks.
@@ -568,6 +570,26 @@ public:
         if (!schur_symbolic_stale()) return;
         schur_explicit_release();   // the old wiring's buffers first: both need not fit together
         if (src_.schur_lists.size() > 16) throw PlanError("generic: ReducedSystem(\"explicit\"): more than 16 instance lists");
+        const size_t cw = (size_t)src_.schur_cr * src_.schur_ce, cc = (size_t)src_.schur_cr * src_.schur_cr;
+        bool built = false;
+        if (symbolic_mode_ != kSymbolicHost) {   // the lists in place, in the eliminated slots' incidence order
+            std::vector<SchurListDev> dl;
+            long long nq = 0;
+            for (auto& l : src_.schur_lists) {
+                dl.push_back({a_.slot[l.eslot], a_.slot[l.rslot], geid_[l.eslot], nedge_[l.graph], 0});
+                nq += nedge_[l.graph];
+            }
+            built = symbolic_device(snpix_[m_.elim_space], snpix_[src_.schur_rspace], dl, false, "explicit Schur complement", 0,
+                                    (long long)(2 * cw * sizeof(T)) * nq, s);
+        }
+        if (!built) schur_symbolic_host(s);
+        sx_val_ = (T*)dmalloc(sizeof(T) * std::max<size_t>(1, cc * sx_nnzb_));
+        sx_w_ = (T*)dmalloc(sizeof(T) * std::max<size_t>(1, cw * sx_nq_));
+        sx_y_ = (T*)dmalloc(sizeof(T) * std::max<size_t>(1, cw * sx_nq_));
+        sx_generation_ = topology_generation_;
+    }
+    // the host builder (schur_pattern.h): the slot arrays down, the pattern up
+    void schur_symbolic_host(hipStream_t s) {
         std::map<int, std::vector<int>> host;   // GenArgs::slot index -> its vertices
         std::vector<SchurList> lists;
         for (auto& l : src_.schur_lists)
@@ -605,11 +627,7 @@ public:
         sx_nlong_ = (int)lng.size();
         sx_long_ = up(lng);
         OPT_HIP_CHECK(hipStreamSynchronize(s));   // (the host vectors go out of scope)
-        const size_t cw = (size_t)src_.schur_cr * src_.schur_ce, cc = (size_t)src_.schur_cr * src_.schur_cr;
-        sx_val_ = (T*)dmalloc(sizeof(T) * std::max<size_t>(1, cc * sx_nnzb_));
-        sx_w_ = (T*)dmalloc(sizeof(T) * std::max<size_t>(1, cw * sx_nq_));
-        sx_y_ = (T*)dmalloc(sizeof(T) * std::max<size_t>(1, cw * sx_nq_));
-        sx_generation_ = topology_generation_;
+        symbolic_host_info();
     }
     void schur_eblk(hipStream_t s) { launch(k_schur_eblk_, s, {&a_, &blk_, &sx_w_, &sx_y_, &sx_qb_}); }
     void schur_assemble(hipStream_t s) {
@@ -634,6 +652,8 @@ public:
         return true;
     }
     long long schur_matrix_pairs() const { return sx_npairs_; }
+    // what the last symbolic phase of S or H did (OptAMD_PlanSymbolicInfo); empty before the first
+    const std::string& symbolic_info() const { return sym_info_; }
     void schur_matrix_copy(int* rowPtr, int* colInd, T* val, hipStream_t s) {
         const long long nR = snpix_[src_.schur_rspace];
         OPT_HIP_CHECK(hipMemcpyAsync(rowPtr, sx_rowptr_, sizeof(int) * (nR + 1), hipMemcpyDefault, s));
@@ -647,7 +667,7 @@ public:
     }
     // ---- the explicitly formed H = J^T J (NormalMatrix("explicit"); StencilPlan: HasNormal;
     // gen/codegen_normal.cpp) ----
-    // Symbolic phase (host, schur_pattern.h with the edge in the eliminated vertex's place):
+    // Symbolic phase (the same two builders with the edge in the eliminated vertex's place):
     // block-CSR pattern, per-block lists of instance pairs and the long rows, built from the
     // vertex arrays at the first use and again when the graphs were re-wired. Numeric phase, once
     // per Step between jtf (the diagonal blocks in blk) and block_init (which inverts them in
@@ -669,6 +689,26 @@ public:
             ebase[g] = ne;
             if (used) ne += nedge_[g];
         }
+        const long long nR = pixels_of(groups_[0].images[0]);
+        const size_t cw = (size_t)src_.normal_c * src_.normal_r, cc = (size_t)src_.normal_c * src_.normal_c;
+        bool built = false;
+        if (symbolic_mode_ != kSymbolicHost) {   // the lists in place: the edge is the vertex, the order the identity
+            std::vector<SchurListDev> dl;
+            long long nq = 0;
+            for (auto& L : src_.normal_lists) {
+                dl.push_back({nullptr, a_.slot[L.slot], nullptr, nedge_[L.graph], ebase[L.graph]});
+                nq += nedge_[L.graph];
+            }
+            built = symbolic_device(ne, nR, dl, true, "NormalMatrix(\"explicit\")", gen::kNormalLongRow,
+                                    (long long)(cw * sizeof(T)) * nq, s);
+        }
+        if (!built) normal_symbolic_host(ebase, ne, nR, s);
+        sx_val_ = (T*)dmalloc(sizeof(T) * std::max<size_t>(1, cc * sx_nnzb_));
+        sx_w_ = (T*)dmalloc(sizeof(T) * std::max<size_t>(1, cw * sx_nq_));
+        sx_generation_ = topology_generation_;
+    }
+    // the host builder (schur_pattern.h): the slot arrays down, the pattern and the long lists up
+    void normal_symbolic_host(const long long* ebase, long long ne, long long nR, hipStream_t s) {
         std::vector<std::vector<int>> host(src_.normal_lists.size()), ids(src_.normal_lists.size());
         for (size_t l = 0; l < src_.normal_lists.size(); ++l) {
             const auto& L = src_.normal_lists[l];
@@ -681,7 +721,6 @@ public:
         std::vector<SchurList> lists;
         for (size_t l = 0; l < src_.normal_lists.size(); ++l)
             lists.push_back({ids[l].data(), host[l].data(), nedge_[src_.normal_lists[l].graph]});
-        const long long nR = pixels_of(groups_[0].images[0]);
         SchurPattern P;
         try {
             schur_pattern_build(ne, nR, lists, &P, true, "NormalMatrix(\"explicit\")");
@@ -712,10 +751,7 @@ public:
         nx_nlongrow_ = (int)lrow.size();
         nx_longrow_ = up(lrow);
         OPT_HIP_CHECK(hipStreamSynchronize(s));   // (the host vectors go out of scope)
-        const size_t cw = (size_t)src_.normal_c * src_.normal_r, cc = (size_t)src_.normal_c * src_.normal_c;
-        sx_val_ = (T*)dmalloc(sizeof(T) * std::max<size_t>(1, cc * sx_nnzb_));
-        sx_w_ = (T*)dmalloc(sizeof(T) * std::max<size_t>(1, cw * sx_nq_));
-        sx_generation_ = topology_generation_;
+        symbolic_host_info();
     }
     void normal_eblk(hipStream_t s) { launch(k_normal_eblk_, s, {&a_, &sx_w_, &sx_qb_}); }
     void normal_assemble(hipStream_t s) {
@@ -963,6 +999,51 @@ private:
         for (const void* p : args) a.push_back(const_cast<void*>(p));
         OPT_HIP_CHECK(hipModuleLaunchKernel(f, grid, 1, 1, kBlock, 1, 1, 0, s, a.data(), nullptr));
     }
+    // The symbolic phase on the device (schur_pattern_dev.hip) into the sx_ buffers; false, with
+    // nothing allocated, where its temporaries do not fit: that wiring takes the host path.
+    bool symbolic_device(long long nE, long long nR, const std::vector<SchurListDev>& lists, bool distinct, const char* what,
+                         int long_row, long long reserve_bytes, hipStream_t s) {
+        SchurPatternDev D;
+        const char* cap = getenv("OPT_AMD_SYMBOLIC_MAX_BYTES");
+        bool built = false;
+        try {
+            built = schur_pattern_build_dev(nE, nR, lists, distinct, what, gen::kSchurLongPairs, long_row, reserve_bytes,
+                                            cap && *cap ? atoll(cap) : -1, s, &D);
+        } catch (const std::length_error& e) {
+            throw PlanError(std::string("generic: ") + e.what());
+        }
+        sym_fallback_ = !built;
+        sym_transient_ = D.transient_bytes;
+        if (!built) return false;
+        for (size_t l = 0; l < lists.size(); ++l) sx_qb_.b[l] = D.base[l];
+        sx_nnzb_ = D.n_blocks;
+        sx_npairs_ = D.n_pairs;
+        sx_nq_ = D.n_instances;
+        sx_rowptr_ = D.rowPtr;
+        sx_colind_ = D.colInd;
+        sx_blkrow_ = D.blkRow;
+        sx_pairptr_ = D.pairPtr;
+        sx_pairs_ = D.pairs;
+        sx_nlong_ = D.n_long;
+        sx_long_ = D.longBlk;
+        if (long_row > 0) {
+            nx_nlongrow_ = D.n_longrow;
+            nx_longrow_ = D.longRow;
+        } else {
+            dfree(D.longRow);
+        }
+        sym_info_ = std::string("path=device reason=") + (symbolic_mode_ == kSymbolicDevice ? "env" : "default") + symbolic_counts();
+        return true;
+    }
+    void symbolic_host_info() {
+        const bool mem = symbolic_mode_ != kSymbolicHost && sym_fallback_;
+        if (!mem) sym_transient_ = 0;
+        sym_info_ = std::string("path=host reason=") + (mem ? "memory" : "env") + symbolic_counts();
+    }
+    std::string symbolic_counts() const {
+        return " pairs=" + std::to_string(sx_npairs_) + " blocks=" + std::to_string(sx_nnzb_) + " instances=" +
+               std::to_string(sx_nq_) + " transient_bytes=" + std::to_string(sym_transient_);
+    }
     void schur_explicit_release() {
         for (int** q : {&sx_rowptr_, &sx_colind_, &sx_blkrow_, &sx_pairptr_, &sx_pairs_, &sx_long_, &nx_longrow_}) { dfree(*q); *q = nullptr; }
         for (T** q : {&sx_val_, &sx_w_, &sx_y_}) { dfree(*q); *q = nullptr; }
@@ -1103,6 +1184,18 @@ private:
     hipFunction_t k_normal_eblk_{}, k_normal_assemble_{}, k_normal_assemble_long_{}, k_normal_spmv_{};
     int* nx_longrow_ = nullptr;
     int nx_nlongrow_ = 0;
+    // where the symbolic phase of either form runs: OPT_AMD_SYMBOLIC=host|device, read when the
+    // plan is made (unset: the device); what the last one did, for symbolic_info()
+    enum { kSymbolicDefault, kSymbolicHost, kSymbolicDevice };
+    static int symbolic_mode_from_env() {
+        const char* v = getenv("OPT_AMD_SYMBOLIC");
+        const std::string w = v ? v : "";
+        return w == "host" ? kSymbolicHost : w == "device" ? kSymbolicDevice : kSymbolicDefault;
+    }
+    const int symbolic_mode_ = symbolic_mode_from_env();
+    bool sym_fallback_ = false;
+    long long sym_transient_ = 0;
+    std::string sym_info_;
 };
 
 static_assert(HasBlockPre<GenericOp<float>>::value);   // the optional driver features this Op claims (stencil_plan.h)

@@ -16,6 +16,7 @@
 #include "plan.h"
 #include "problem.h"
 #include "schur_pattern.h"
+#include "schur_pattern_dev.h"
 
 static_assert(sizeof(Opt_InitializationParameters) == 44,
               "Opt_InitializationParameters must keep the reference layout (Opt.h:10-35)");
@@ -262,6 +263,12 @@ int OptAMD_ApplyReduced(Opt_State* state, Opt_Plan* plan, void** params, const v
 int OptAMD_PlanReducedMatrixShape(Opt_Plan* plan, long long* blockRows, int* blockDim, long long* nnzBlocks) {
     if (!valid_plan(plan, "OptAMD_PlanReducedMatrixShape")) return -1;
     return plan->impl->reduced_matrix_shape(blockRows, blockDim, nnzBlocks) ? 1 : 0;
+}
+int OptAMD_PlanSymbolicInfo(Opt_Plan* plan, char* buf, int n) {
+    if (!valid_plan(plan, "OptAMD_PlanSymbolicInfo")) return -1;
+    std::string line;
+    if (plan->impl->symbolic_info(&line) < 0) return -1;
+    return copy_name(line, buf, n);
 }
 int OptAMD_ReducedMatrix(Opt_Plan* plan, void** params, int* rowPtr, int* colInd, void* val) {
     if (!valid_plan(plan, "OptAMD_ReducedMatrix")) return 1;
@@ -524,9 +531,10 @@ int OptAMD_GenericPlanCheck(const char* filename, char* buf, int n) {
     copy_name(why, buf, n);
     return r;
 }
-int OptAMD_SchurPattern(long long nEliminated, long long nRetained, int nLists, const int* const* elimVertex,
-                        const int* const* retVertex, const long long* nEdges, long long* counts, int* rowPtr,
-                        int* colInd, int* pairPtr, int* pairs, char* buf, int n) {
+// OptAMD_SchurPattern / OptAMD_SchurPatternDevice: the same checks and outputs, the builder differs
+static int schur_pattern_api(bool device, long long nEliminated, long long nRetained, int nLists,
+                             const int* const* elimVertex, const int* const* retVertex, const long long* nEdges,
+                             long long* counts, int* rowPtr, int* colInd, int* pairPtr, int* pairs, char* buf, int n) {
     if (nEliminated < 0 || nRetained < 0 || nLists < 0 || (nLists && (!elimVertex || !retVertex || !nEdges)))
         return copy_name("invalid arguments", buf, n), -1;
     std::vector<optamd::SchurList> lists;
@@ -538,7 +546,8 @@ int OptAMD_SchurPattern(long long nEliminated, long long nRetained, int nLists, 
     }
     optamd::SchurPattern P;
     try {
-        optamd::schur_pattern_build(nEliminated, nRetained, lists, &P);
+        if (device) optamd::schur_pattern_build_dev_host(nEliminated, nRetained, lists, false, "explicit Schur complement", &P);
+        else optamd::schur_pattern_build(nEliminated, nRetained, lists, &P);
     } catch (const std::exception& e) {
         return copy_name(e.what(), buf, n), -1;
     }
@@ -549,9 +558,21 @@ int OptAMD_SchurPattern(long long nEliminated, long long nRetained, int nLists, 
     if (pairs) std::copy(P.pairs.begin(), P.pairs.end(), pairs);
     return 0;
 }
-int OptAMD_NormalPattern(long long nVertices, int nLists, const int* const* vertex, const int* listGraph,
-                         const long long* graphEdges, int nGraphs, long long* counts, int* rowPtr, int* colInd,
-                         int* pairPtr, int* pairs, char* buf, int n) {
+int OptAMD_SchurPattern(long long nEliminated, long long nRetained, int nLists, const int* const* elimVertex,
+                        const int* const* retVertex, const long long* nEdges, long long* counts, int* rowPtr,
+                        int* colInd, int* pairPtr, int* pairs, char* buf, int n) {
+    return schur_pattern_api(false, nEliminated, nRetained, nLists, elimVertex, retVertex, nEdges, counts, rowPtr, colInd,
+                             pairPtr, pairs, buf, n);
+}
+int OptAMD_SchurPatternDevice(long long nEliminated, long long nRetained, int nLists, const int* const* elimVertex,
+                              const int* const* retVertex, const long long* nEdges, long long* counts, int* rowPtr,
+                              int* colInd, int* pairPtr, int* pairs, char* buf, int n) {
+    return schur_pattern_api(true, nEliminated, nRetained, nLists, elimVertex, retVertex, nEdges, counts, rowPtr, colInd,
+                             pairPtr, pairs, buf, n);
+}
+static int normal_pattern_api(bool device, long long nVertices, int nLists, const int* const* vertex, const int* listGraph,
+                              const long long* graphEdges, int nGraphs, long long* counts, int* rowPtr, int* colInd,
+                              int* pairPtr, int* pairs, char* buf, int n) {
     if (nVertices < 0 || nLists < 0 || nGraphs < 0 || (nLists && (!vertex || !listGraph || !graphEdges)))
         return copy_name("invalid arguments", buf, n), -1;
     std::vector<long long> ebase(nGraphs + 1, 0);
@@ -576,7 +597,8 @@ int OptAMD_NormalPattern(long long nVertices, int nLists, const int* const* vert
     }
     optamd::SchurPattern P;
     try {
-        optamd::schur_pattern_build(ebase[nGraphs], nVertices, lists, &P, true, "NormalMatrix(\"explicit\")");
+        if (device) optamd::schur_pattern_build_dev_host(ebase[nGraphs], nVertices, lists, true, "NormalMatrix(\"explicit\")", &P);
+        else optamd::schur_pattern_build(ebase[nGraphs], nVertices, lists, &P, true, "NormalMatrix(\"explicit\")");
     } catch (const std::exception& e) {
         return copy_name(e.what(), buf, n), -1;
     }
@@ -586,6 +608,18 @@ int OptAMD_NormalPattern(long long nVertices, int nLists, const int* const* vert
     if (pairPtr) std::copy(P.pairPtr.begin(), P.pairPtr.end(), pairPtr);
     if (pairs) std::copy(P.pairs.begin(), P.pairs.end(), pairs);
     return 0;
+}
+int OptAMD_NormalPattern(long long nVertices, int nLists, const int* const* vertex, const int* listGraph,
+                         const long long* graphEdges, int nGraphs, long long* counts, int* rowPtr, int* colInd,
+                         int* pairPtr, int* pairs, char* buf, int n) {
+    return normal_pattern_api(false, nVertices, nLists, vertex, listGraph, graphEdges, nGraphs, counts, rowPtr, colInd,
+                              pairPtr, pairs, buf, n);
+}
+int OptAMD_NormalPatternDevice(long long nVertices, int nLists, const int* const* vertex, const int* listGraph,
+                               const long long* graphEdges, int nGraphs, long long* counts, int* rowPtr, int* colInd,
+                               int* pairPtr, int* pairs, char* buf, int n) {
+    return normal_pattern_api(true, nVertices, nLists, vertex, listGraph, graphEdges, nGraphs, counts, rowPtr, colInd,
+                              pairPtr, pairs, buf, n);
 }
 int OptAMD_GenericDescribe(const char* filename, char* buf, int n) {
     std::string text, out;

@@ -183,6 +183,13 @@ public:
         (void)params; (void)rowPtr; (void)colInd; (void)val;
         return 1;
     }
+    // Where the last symbolic phase of the explicit S or H ran and how large it was
+    // (OptAMD_PlanSymbolicInfo): 0 and one line of key=value words, empty before the first
+    // symbolic phase; -1 on a plan with neither statement.
+    virtual int symbolic_info(std::string* line) const {
+        (void)line;
+        return -1;
+    }
     // The explicitly formed H = J^T J (NormalMatrix("explicit"), include/opt_amd.h): the same
     // pair of calls for the normal matrix of a plan whose energy has that statement.
     virtual bool normal_matrix_shape(long long* rows, int* dim, long long* nnzb) const {

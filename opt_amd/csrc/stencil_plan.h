@@ -103,7 +103,7 @@ __global__ __launch_bounds__(kBlock) void revert_images_kernel(VecLayout L, cons
 //                          schur_elim, schur_apply, schur_back, and for ReducedSystem("explicit")
 //                          schur_explicit(), schur_symbolic_stale, schur_symbolic, schur_eblk,
 //                          schur_assemble, schur_spmv, schur_matrix_shape, schur_matrix_copy,
-//                          schur_explicit_key
+//                          schur_explicit_key, symbolic_info
 //   HasNormal              normal(); normal_symbolic_stale, normal_symbolic, normal_eblk,
 //                          normal_assemble, normal_spmv, normal_matrix_shape, normal_matrix_copy,
 //                          normal_key
@@ -203,7 +203,7 @@ OPTAMD_OP_TRAIT(HasSchur, schur);
 // Ops that can form H = J^T J explicitly (GenericOp for NormalMatrix("explicit")): normal() says
 // whether this energy asked for it (then block_pre() holds too, and schur() does not). Once per
 // Step, after jtf has left the diagonal blocks in the block buffer and before block_init inverts
-// them, normal_symbolic (host, only after a re-wiring), normal_eblk and normal_assemble build H
+// them, normal_symbolic (only after a re-wiring), normal_eblk and normal_assemble build H
 // in block-CSR; every apply of the PCG loop — and the residual reset's, and apply_jtj's — is then
 // normal_spmv, with apply's contract. LM's diagonal is not part of H: the SpMV adds dadd p.
 OPTAMD_OP_TRAIT(HasNormal, normal);
@@ -633,6 +633,14 @@ public:
         }
         return Plan::reduced_matrix(params, rowPtr, colInd, val);
     }
+    // what the last symbolic phase of S or H did; -1 on a plan with neither statement
+    int symbolic_info(std::string* line) const override {
+        if constexpr (HasSchur<Op>::value)
+            if (explicit_) return *line = op_->symbolic_info(), 0;
+        if constexpr (HasNormal<Op>::value)
+            if (normal_) return *line = op_->symbolic_info(), 0;
+        return Plan::symbolic_info(line);
+    }
     bool normal_matrix_shape(long long* rows, int* dim, long long* nnzb) const override {
         if constexpr (HasNormal<Op>::value)
             if (normal_) return op_->normal_matrix_shape(rows, dim, nnzb);
@@ -856,7 +864,7 @@ private:
         if (timed) tend();
         OPT_HIP_CHECK(hipGetLastError());
     }
-    // explicit plans: the pattern of S for the graphs as bound (host; a no-op while the wiring
+    // explicit plans: the pattern of S for the graphs as bound (a no-op while the wiring
     // stands). A rebuild moves the SpMV's buffers, so no captured loop survives it.
     void schur_symbolic() {
         if constexpr (HasSchur<Op>::value)
@@ -868,7 +876,7 @@ private:
             }
     }
 
-    // NormalMatrix("explicit") plans: the pattern of H for the graphs as bound (host; a no-op
+    // NormalMatrix("explicit") plans: the pattern of H for the graphs as bound (a no-op
     // while the wiring stands). A rebuild moves the SpMV's buffers, so no captured loop survives.
     void normal_symbolic() {
         if constexpr (HasNormal<Op>::value)

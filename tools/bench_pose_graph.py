@@ -135,6 +135,9 @@ def run_variants(a):
         rows, dim, nnzb = s2.normal_matrix_shape()
         e = out["explicit"]
         e["symbolic_build_ms"] = ms
+        if hasattr(s2.lib, "OptAMD_PlanSymbolicInfo"):   # (a library from before the device builder has none)
+            info = dict(kv.split("=") for kv in s2.symbolic_info().split())
+            e["symbolic_path"], e["symbolic_transient_bytes"] = info["path"], int(info["transient_bytes"])
         e["block_rows"], e["block_dim"], e["blocks"] = rows, dim, nnzb
         e["matrix_bytes"] = nnzb * dim * dim * 4
         # what one SpMV moves: values, column indices, row pointers, p once per block, Ap and p once per row

@@ -177,6 +177,9 @@ def main():
         rows, dim, nnzb = s2.reduced_matrix_shape()
         e = out["explicit"]
         e["symbolic_build_ms"] = ms
+        if hasattr(s2.lib, "OptAMD_PlanSymbolicInfo"):   # (a library from before the device builder has none)
+            info = dict(kv.split("=") for kv in s2.symbolic_info().split())
+            e["symbolic_path"], e["symbolic_transient_bytes"] = info["path"], int(info["transient_bytes"])
         e["block_rows"], e["block_dim"], e["blocks"] = rows, dim, nnzb
         e["spmv_bytes"] = nnzb * dim * dim * 4
         spmv = e["kernels"].get("schur_spmv", {}).get("us_per_launch", 0.0)
