@@ -96,6 +96,31 @@ int OptAMD_ApplyPreconditioner(Opt_State* state, Opt_Plan* plan, void** problemp
  * -1 for a NULL plan. */
 int OptAMD_PlanEliminated(Opt_Plan* plan, int maxImages, int* eliminated);
 
+/* Robust losses: RobustEnergy(kind, scale, term, ...) in the energy file (generated kernels;
+ * INTEGRATION.md, "Robust losses"). The statement's scalar residuals f_1..f_R form one loss
+ * block per edge of their graph, s = sum f_k^2; kind "huber" (rho = s up to a^2, then
+ * 2 a sqrt(s) - a^2) or "cauchy" (rho = a^2 log(1 + s / a^2)); the scale a is a positive number
+ * or a float Param, re-read whenever the weights are evaluated. The cost is 1/2 sum rho(s) plus
+ * the plain terms; each linearisation is that of the reweighted problem f~ = w f, J~ = w J with
+ * w = sqrt(rho'(s)) held constant (IRLS, no second-order correction), one cached weight per
+ * edge. At most 4 statements per file.
+ *
+ * Writes, for each loss group (statement order, up to maxGroups), its graph, its residuals per
+ * edge and its kind (0 huber, 1 cauchy); any array may be NULL. Returns the number of groups:
+ * 0 on a plan without the statement, -1 for a NULL plan. */
+int OptAMD_PlanLossGroups(Opt_Plan* plan, int maxGroups, int* graph, int* residuals, int* kind);
+
+/* Edges of loss group `group`'s graph (the length of OptAMD_EvalLossWeights' array); -1 for a
+ * NULL plan or a group the plan does not have. */
+long long OptAMD_PlanLossGroupEdges(Opt_Plan* plan, int group);
+
+/* rho'(s) of every edge of loss group `group` at the bound unknowns, in edge order, into
+ * `weights`: an array of the plan's precision with the graph's edge count (a device array;
+ * a host array on a backend_cpu state). Note rho', not its root: 1 on an inlier of the Huber
+ * loss, below 1 where the loss bends. Returns 0; 1 on a plan without the statement; 1 with
+ * OptAMD_PlanError set for a group out of range. */
+int OptAMD_EvalLossWeights(Opt_State* state, Opt_Plan* plan, void** problemparams, int group, void* weights);
+
 /* Sp = S p at the current unknowns (device vectors of OptAMD_PlanUnknownCount elements;
  * on an LMGPU plan with CtC_r p and M at the plan's current trust-region radius). The
  * eliminated entries of p are ignored, those of Sp are 0. Returns 0, or 1 on a plan without

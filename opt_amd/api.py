@@ -66,6 +66,10 @@ _SIGNATURES = [
     ("OptAMD_ApplyPreconditioner", ctypes.c_int, [_VP, _VP, ctypes.POINTER(_VP), _VP, _VP]),
     ("OptAMD_PlanEliminated", ctypes.c_int, [_VP, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
     ("OptAMD_ApplyReduced", ctypes.c_int, [_VP, _VP, ctypes.POINTER(_VP), _VP, _VP]),
+    ("OptAMD_PlanLossGroups", ctypes.c_int, [_VP, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
+                                             ctypes.POINTER(ctypes.c_int)]),
+    ("OptAMD_PlanLossGroupEdges", ctypes.c_longlong, [_VP, ctypes.c_int]),
+    ("OptAMD_EvalLossWeights", ctypes.c_int, [_VP, _VP, ctypes.POINTER(_VP), ctypes.c_int, _VP]),
     ("OptAMD_TimeApplyJTJ", ctypes.c_double, [_VP, _VP, ctypes.POINTER(_VP), _VP, _VP, ctypes.c_int]),
     ("OptAMD_SetKernelTiming", None, [_VP, ctypes.c_int]),
     ("OptAMD_KernelStat", ctypes.c_int, [_VP, ctypes.c_char_p, ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_double)]),
@@ -341,6 +345,30 @@ class OptSolver:
         if k < 0:
             raise OptError("OptAMD_PlanEliminated failed")
         return list(f)[:k]
+
+    def loss_groups(self):
+        """The plan's robust-loss groups, one dict per RobustEnergy statement of the energy file
+        (OptAMD_PlanLossGroups): graph id, residuals per edge, kind ("huber" / "cauchy") and the
+        graph's edge count. [] on a plan without the statement."""
+        g, r, k = (ctypes.c_int * 4)(), (ctypes.c_int * 4)(), (ctypes.c_int * 4)()
+        n = self.lib.OptAMD_PlanLossGroups(self.plan, 4, g, r, k)
+        if n < 0:
+            raise OptError("OptAMD_PlanLossGroups failed")
+        return [{"graph": g[i], "residuals": r[i], "kind": ("huber", "cauchy")[k[i]],
+                 "edges": self.lib.OptAMD_PlanLossGroupEdges(self.plan, i)} for i in range(n)]
+
+    def loss_weights(self, problem_params, group: int = 0):
+        """rho'(s) per edge of one loss group at the bound unknowns, in edge order
+        (OptAMD_EvalLossWeights): 1 on a Huber inlier, below 1 where the loss bends. A torch
+        tensor on the plan's device; raises on a plan without RobustEnergy or a bad group."""
+        import torch
+        edges = self.lib.OptAMD_PlanLossGroupEdges(self.plan, group)
+        w = torch.empty(max(edges, 1), dtype=torch.float64 if self.double_precision else torch.float32, device="cuda")
+        pk = ParamPack(problem_params)
+        if self.lib.OptAMD_EvalLossWeights(self.state, self.plan, pk.ptr, group, _ptr(w)):
+            self._raise_plan_error()
+            raise OptError("OptAMD_EvalLossWeights failed (the plan has no RobustEnergy statement)")
+        return w[:max(edges, 0)]
 
     def apply_reduced(self, problem_params, p, Sp) -> None:
         """Sp = S p, the Schur complement's product at the current unknowns

@@ -124,7 +124,8 @@ void emit_prelude(const Ctx& cx, std::ostringstream& o) {
     o << "typedef " << (dbl ? "double" : "float") << " T;\n";
     o << "typedef T OptV4 __attribute__((ext_vector_type(4)));\n";
     o << "struct GenArgs { " << OPTAMD_STR(OPTAMD_GENARGS_FIELDS)
-      << (m.multi() ? " " OPTAMD_STR(OPTAMD_GENARGS_SPACES) : "") << " };\n";
+      << (m.multi() || !m.loss.empty() ? " " OPTAMD_STR(OPTAMD_GENARGS_SPACES) : "")
+      << (!m.loss.empty() ? " " OPTAMD_STR(OPTAMD_GENARGS_LOSS) : "") << " };\n";
     o << kReduceDevSrc << "\n";
     o << "#define OPT_COORDS const int W = a.dims[0], H = a.dims[1], D = a.dims[2]; (void)D;\n";
     o << "__device__ __forceinline__ void opt_sincos(float x, float* s, float* c) { sincosf(x, s, c); }\n"
@@ -737,6 +738,7 @@ void emit_dump_j(Ctx& cx, std::ostringstream& o) {
     for (auto& r : m.residuals)
         if (std::find(order.begin(), order.end(), r.graph) == order.end()) order.push_back(r.graph);
     if (cx.mspace) order.clear();  // no Jacobian dump over several index spaces (the plan refuses it)
+    if (cx.has_loss()) order.clear();  // nor with a RobustEnergy statement (J~ = W J is the plan's own matter)
     for (size_t si = 0; si < order.size(); ++si) {
         const int g = order[si];
         std::vector<const GResidual*> rs;
@@ -800,6 +802,94 @@ void emit_dump_j(Ctx& cx, std::ostringstream& o) {
         }
         o << "    }\n}\n";
     }
+}
+
+// ------------------------------------------------ RobustEnergy: weights and rho
+std::function<std::string(int)> Ctx::weight_at_q(int sbk) const {
+    if (!has_loss()) return nullptr;
+    return [this, sbk](int group) {
+        const auto it = std::find(gs.loss_inc.begin(), gs.loss_inc.end(), std::make_pair(group, sbk));
+        if (it == gs.loss_inc.end()) {
+            fprintf(stderr, "[opt_amd] codegen: loss group %d has no incidence-order weights at slot %d\n", group, sbk);
+            abort();
+        }
+        const std::string base = "(const T*)a.lwq[" + std::to_string(it - gs.loss_inc.begin()) + "]";
+        return off32 ? "opt_g32(" + base + ", q, 1, 0)" : "(" + base + ")[q]";
+    };
+}
+std::function<std::string(int)> Ctx::weight_at_e() const {
+    if (!has_loss()) return nullptr;
+    return [](int group) { return "((const T*)a.lwe[" + std::to_string(group) + "])[e]"; };
+}
+// Ceres' definitions on s (Robust losses); neither divides by zero at s = 0:
+// Huber's a / sqrt(s) is computed there and not selected
+void loss_rho(const Ctx& cx, Body& b, int g, const std::string& s, bool rho) {
+    const GLossGroup& L = cx.m.loss[g];
+    const std::string G = std::to_string(g), a = "la" + G, a2 = "la2_" + G;
+    b.line("const T " + a + " = " + (L.scale_param >= 0 ? "(T)a.prm[" + std::to_string(L.scale_param) + "]" : lit(L.scale)) +
+           ", " + a2 + " = " + a + " * " + a + ";");
+    if (L.kind == GLossGroup::Huber) {
+        b.line("const bool lin" + G + " = " + s + " <= " + a2 + "; const T lr" + G + " = sqrt(" + s + ");");
+        b.line("const T rho1" + G + " = lin" + G + " ? (T)1 : " + a + " / lr" + G + ";");
+        if (rho) b.line("const T rho" + G + " = lin" + G + " ? " + s + " : (T)2 * " + a + " * lr" + G + " - " + a2 + ";");
+    } else {
+        b.line("const T lq" + G + " = " + s + " / " + a2 + ";");
+        b.line("const T rho1" + G + " = (T)1 / ((T)1 + lq" + G + ");");
+        if (rho) b.line("const T rho" + G + " = " + a2 + " * log1p(lq" + G + ");");
+    }
+}
+// s of loss group g at this edge from its raw residuals: declares ls<g>
+static void loss_s(Ctx& cx, Body& b, int g) {
+    std::string sum = "(T)0";
+    for (int f : cx.m.loss[g].raw) {
+        const std::string v = b.v(f);
+        sum += " + " + v + " * " + v;
+    }
+    b.line("const T ls" + std::to_string(g) + " = " + sum + ";");
+}
+// gen_loss_weights: one thread per edge, gen_cost's edge loop. Per loss group: the raw
+// residuals, s, w = sqrt(rho'(s)) stored in edge order (lwe) and, once per slot that carries
+// unknowns, at the edge's position in that slot's incidence list (lwq through lpos) — the
+// gathers then read their weight at q beside gnb[..][q] instead of through geid. With rho1_out
+// (OptAMD_EvalLossWeights): rho'(s) of group `only` to the caller's array, the caches untouched.
+void emit_loss_weights(Ctx& cx, std::ostringstream& o) {
+    const GModel& m = cx.m;
+    GenSource& gs = cx.gs;
+    if (!cx.has_loss()) return;
+    gs.has_loss = true;
+    const bool prefetch_nb = cx.knobs.prefetch_nb;
+    o << "extern \"C\" __global__ __launch_bounds__(256) void gen_loss_weights(GenArgs a, T* __restrict__ rho1_out, int only) {\n"
+      << cx.top_coords();
+    for (size_t G = 0; G < m.loss.size(); ++G) {
+        const int g = m.loss[G].graph;
+        const size_t ns = m.graphs[g].slot_names.size();
+        auto sl = [&](size_t s) { return "a.slot[" + std::to_string(gs.slot_base[g] + s) + "]"; };
+        o << "    if (only < 0 || only == " << G << ") {\n"
+          << "    const long long es = (long long)gridDim.x * 256, ne = a.nedge[" << g << "];\n"
+          << "    long long e = opt_xcd_block() * 256 + threadIdx.x;\n";
+        if (prefetch_nb)
+            for (size_t s = 0; s < ns; ++s) o << "    int n" << s << " = e < ne ? " << sl(s) << "[e] : 0;\n";
+        o << "    for (; e < ne; e += es) {\n";
+        for (size_t s = 0; s < ns; ++s)
+            o << "        const int v" << s << " = " << (prefetch_nb ? "n" + std::to_string(s) : sl(s) + "[e]") << ";\n";
+        if (prefetch_nb) {
+            o << "        if (e + es < ne) {";
+            for (size_t s = 0; s < ns; ++s) o << " n" << s << " = " << sl(s) << "[e + es];";
+            o << " }\n";
+        }
+        Body b(cx, o, cx.nd);
+        loss_s(cx, b, (int)G);
+        loss_rho(cx, b, (int)G, "ls" + std::to_string(G), false);
+        const std::string Gs = std::to_string(G);
+        b.line("if (rho1_out) { rho1_out[e] = rho1" + Gs + "; continue; }");
+        b.line("const T lw = sqrt(rho1" + Gs + ");");
+        b.line("((T*)a.lwe[" + Gs + "])[e] = lw;");
+        for (size_t i = 0; i < gs.loss_inc.size(); ++i)
+            if (gs.loss_inc[i].first == (int)G)
+                b.line("((T*)a.lwq[" + std::to_string(i) + "])[a.lpos[" + std::to_string(gs.loss_inc[i].second) + "][e]] = lw;");
+        o << "    }\n    }\n";
+    }
+    o << "}\n";
 }
 
 // ------------------------------------------------------- cost (centres + edges)
@@ -869,12 +959,30 @@ void emit_cost(Ctx& cx, std::ostringstream& o) {
         }
         Body b(cx, o, cx.nd);
         std::string sum = "(T)0";
+        // RobustEnergy: per loss group of this graph s, rho(s), rho'(s) from the raw residuals and
+        // w recomputed inline (the expression gen_loss_weights caches). Its templates W f_k then
+        // go through the same q_k as the plain ones; their squares are summed apart (lsum): the
+        // cost takes rho(s), the model cost rho(s) - rho'(s) s + sum_k (f~_k + J~_k delta)^2
+        std::string lsum = "(T)0", lrho = "(T)0", lconst = "(T)0";
+        bool lossy = false;
+        for (size_t G = 0; G < m.loss.size(); ++G) {
+            if (m.loss[G].graph != (int)g) continue;
+            const std::string Gs = std::to_string(G);
+            lossy = true;
+            loss_s(cx, b, (int)G);
+            loss_rho(cx, b, (int)G, "ls" + Gs, true);
+            b.line("const T lw" + Gs + " = sqrt(rho1" + Gs + ");");
+            lrho += " + rho" + Gs;
+            lconst += " + (rho" + Gs + " - rho1" + Gs + " * ls" + Gs + ")";
+        }
+        if (lossy) b.weight_at([](int G) { return "lw" + std::to_string(G); });
         int idx = 0;
-        for (auto& r : m.residuals) {
+        for (size_t ri = 0; ri < m.residuals.size(); ++ri) {
+            const GResidual& r = m.residuals[ri];
             if (r.graph != (int)g) continue;
             std::string e = b.v(r.expr);
             b.line("T q" + std::to_string(idx) + " = " + e + ";");
-            sum += " + q" + std::to_string(idx) + " * q" + std::to_string(idx);
+            (lossy && m.loss_group_of((int)ri) >= 0 ? lsum : sum) += " + q" + std::to_string(idx) + " * q" + std::to_string(idx);
             ++idx;
         }
         b.line("if (delta) {");
@@ -893,6 +1001,7 @@ void emit_cost(Ctx& cx, std::ostringstream& o) {
         }
         b.line("}");
         b.line("acc += (T)0.5 * (" + sum + ");");
+        if (lossy) b.line("acc += (T)0.5 * (delta ? " + lconst + " + " + lsum + " : " + lrho + ");");
         o << "    }\n    }\n";
     }
     o << "    double v[1] = {(double)acc};\n    block_reduce_publish<1>(v, rs, blockIdx.x);\n}\n";
@@ -907,6 +1016,15 @@ GenSource generate(GModel& m, bool dbl, bool off32) {
         sb += (int)m.graphs[g].slot_names.size();
     }
     for (auto& r : m.residuals) (r.graph < 0 ? gs.has_centered : gs.has_graph) = true;
+    // RobustEnergy: one incidence-order weights array per (group, slot through which one of the
+    // group's residuals reads an unknown): the slots whose gathers evaluate the group
+    for (size_t G = 0; G < m.loss.size(); ++G)
+        for (int ri : m.loss[G].residuals)
+            for (int u : m.residuals[ri].unknowns) {
+                const std::pair<int, int> key((int)G, gs.slot_base[m.loss[G].graph] + m.pool.at(u).slot);
+                if (std::find(gs.loss_inc.begin(), gs.loss_inc.end(), key) == gs.loss_inc.end()) gs.loss_inc.push_back(key);
+            }
+    std::sort(gs.loss_inc.begin(), gs.loss_inc.end());
 
     std::ostringstream o;
     emit_prelude(cx, o);
@@ -921,6 +1039,7 @@ GenSource generate(GModel& m, bool dbl, bool off32) {
     if (cx.tiled) emit_strips(cx, o);
     emit_dump_j(cx, o);
     emit_cost(cx, o);
+    emit_loss_weights(cx, o);
     emit_graph_gathers(cx, o);
     emit_block_pcg(cx, o);
     emit_schur(cx, o);

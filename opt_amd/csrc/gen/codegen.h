@@ -10,6 +10,8 @@
 // macro bodies are compiled on the host and pasted, stringised, into the generated code.
 // The per-space tail is pasted only for energies over several index spaces (GModel::multi):
 // a single-space energy's kernels declare, and the runtime copies, the head alone.
+// An energy with a RobustEnergy statement pastes both tails (the loss tail follows the spaces'
+// on the host); every other energy's argument block, and with it its source, is unchanged.
 #define OPTAMD_GENARGS_FIELDS                                                               \
         int dims[3];                /* unknowns' index space, unused dims = 1 */            \
         long long npix;             /* elements of that space */                            \
@@ -24,6 +26,10 @@
         long long uoff[4];          /* offset of each unknown image in the vector */        \
         int ymem0;                  /* 2-D row slabs: global row of memory row 0 */          \
         long long own_lo, own_hi;   /* owned pixels (memory indices) */
+#define OPTAMD_GENARGS_LOSS                                                                 \
+        void* lwe[4];               /* per loss group: its edges' weights (T), edge order */ \
+        void* lwq[16];              /* per (group, slot) of GenSource::loss_inc: the same weights in that slot's incidence order */ \
+        const int* lpos[16];        /* per slot: position of each edge in the slot's incidence list */
 #define OPTAMD_GENARGS_SPACES                                                               \
         int sdims[8][3];            /* per space: its dims, unused dims = 1 */               \
         long long snpix[8];         /* per space: its elements */                            \
@@ -33,6 +39,7 @@ namespace optamd {
 struct GenArgs {
     OPTAMD_GENARGS_FIELDS
     OPTAMD_GENARGS_SPACES
+    OPTAMD_GENARGS_LOSS
 };
 namespace gen {
 
@@ -94,6 +101,11 @@ struct GenSource {
     int normal_c = 0, normal_r = 0, normal_space = -1;
     struct NormalList { int graph; int slot; };
     std::vector<NormalList> normal_lists;
+    // RobustEnergy (GModel::loss): gen_loss_weights emitted. loss_inc[i] = (group, GenArgs::slot
+    // index): GenArgs::lwq[i] holds that group's weights in that slot's incidence order — one
+    // entry per slot through which the group's residuals read an unknown
+    bool has_loss = false;
+    std::vector<std::pair<int, int>> loss_inc;
 };
 
 // Generate the kernels for `m` in float (dbl = false) or double. off32: every array a

@@ -2,6 +2,7 @@
 // expressions, one local temporary per node and kernel body.
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include "codegen_ctx.h"
 
 namespace optamd {
@@ -65,7 +66,7 @@ bool Body::invariant(int id) {
     switch (n.op) {
         case Op::Const: case Op::Param: r = true; break;
         case Op::Read: r = n.slot == self_ && (n.g < 0 || n.g == graph_); break;
-        case Op::InBox: case Op::Coord: case Op::Sample: r = false; break;
+        case Op::InBox: case Op::Coord: case Op::Sample: case Op::Weight: r = false; break;
         default:
             r = (n.a < 0 || invariant(n.a)) && (n.b < 0 || invariant(n.b)) && (n.d < 0 || invariant(n.d));
     }
@@ -140,6 +141,13 @@ std::string Body::v(int id) {
         case Op::Const: done_[id] = lit(n.c); return done_[id];
         case Op::Param: e = "(T)a.prm[" + std::to_string(n.i) + "]"; break;
         case Op::Read: e = read(n, nullptr); break;
+        case Op::Weight:
+            if (!weight_) {
+                fprintf(stderr, "[opt_amd] codegen: a loss group's weight in a kernel that has no place to read it\n");
+                abort();
+            }
+            e = weight_(n.i);
+            break;
         case Op::Coord: e = "(T)(" + std::string(1, "xyz"[n.i]) + " + " + std::to_string(n.off[n.i]) + ")"; break;
         case Op::Add: e = v(n.a) + " + " + v(n.b); break;
         case Op::Sub: e = v(n.a) + " - " + v(n.b); break;

@@ -142,6 +142,12 @@ struct Ctx : Analysis {
     bool schur() const { return elim_group >= 0; }
     int elim_space() const { return groups[elim_group].space; }
     std::function<std::string(int image, const char* vname)> vec_base;
+    // RobustEnergy (GModel::loss): the weight loads of a Body (Body::weight_at). weight_at_q: the
+    // gather over GenArgs::slot index sbk reads GenArgs::lwq[i][q], i the place of (group, sbk)
+    // in GenSource::loss_inc; weight_at_e: a per-edge kernel reads GenArgs::lwe[group][e]
+    bool has_loss() const { return !m.loss.empty(); }
+    std::function<std::string(int)> weight_at_q(int sbk) const;
+    std::function<std::string(int)> weight_at_e() const;
 };
 inline int tri(int i, int j) { return i >= j ? i * (i + 1) / 2 + j : j * (j + 1) / 2 + i; }
 
@@ -177,6 +183,10 @@ public:
     // register-strip emission (RowWindows): centred reads come from the caller's row
     // windows instead of memory
     void centred_reads(std::function<std::string(const Node&, const char*)> f) { centred_ = std::move(f); }
+    // RobustEnergy: where this body reads loss group g's weight (Op::Weight) — the incidence-order
+    // copy at q in a gather, the edge-order copy at e in a per-edge kernel (Ctx::weight_at_q /
+    // weight_at_e), or a value the kernel has computed itself (gen_cost)
+    void weight_at(std::function<std::string(int)> f) { weight_ = std::move(f); }
 
 private:
     bool invariant(int id);
@@ -203,6 +213,7 @@ private:
     int self_ = -1, graph_ = -1;
     std::map<int, bool> inv_;
     std::function<std::string(const Node&, const char*)> centred_;
+    std::function<std::string(int)> weight_;
 };
 
 // The emitters, in emission order (generate() calls them so; each appends its kernels to o).
@@ -221,6 +232,10 @@ void emit_dump_j(Ctx& cx, std::ostringstream& o);                    // gen_dump
 // gen_cost's per-centre terms over residuals `res`: T s = sum r^2, or with delta sum (r + J delta)^2
 void centred_cost_terms(Ctx& cx, Body& b, const std::vector<int>& res);
 void emit_cost(Ctx& cx, std::ostringstream& o);                      // gen_cost
+void emit_loss_weights(Ctx& cx, std::ostringstream& o);              // gen_loss_weights (RobustEnergy)
+// loss group g at an edge whose raw residuals' squares sum to `s` (a T temporary): declares
+// rho1<g> = rho'(s) and, with `rho`, rho<g> = rho(s)
+void loss_rho(const Ctx& cx, Body& b, int g, const std::string& s, bool rho);
 void emit_graph_gathers(Ctx& cx, std::ostringstream& o);             // gen_jtf_graph, gen_apply_graph
 void emit_block_pcg(const Ctx& cx, std::ostringstream& o);           // gen_blk_*
 // One vertex's gather over its incidence lists (codegen_graph.cpp): J^T F's terms, or with

@@ -47,6 +47,9 @@ void graph_gather(Ctx& cx, std::ostringstream& o, bool apply, int sp, int schur)
             std::ostringstream pre, body;
             Body b(cx, body, cx.nd_of(sp));   // (slot reads use no coordinates)
             b.hoist_to(&pre, (int)k, (int)g);
+            // RobustEnergy: the group's weight at q, streaming beside the gnb copies (loading it one
+            // edge ahead as the vertex ids are measured no gain: DESIGN.md §3.6)
+            if (cx.has_loss()) b.weight_at(cx.weight_at_q(sbk));
             int idx = 0;
             for (auto& r : m.residuals) {
                 if (r.graph != (int)g) continue;

@@ -86,6 +86,7 @@ void emit_normal(Ctx& cx, std::ostringstream& o) {
             o << "        const int v" << s << " = a.slot[" << gs.slot_base[g] + s << "][e];\n";
         std::ostringstream body;
         Body b(cx, body, cx.nd);
+        if (cx.has_loss()) b.weight_at(cx.weight_at_e());
         // entry (row, residual) of each list's G: the partial's temporary, "" = 0
         std::vector<std::vector<std::string>> G(nslots, std::vector<std::string>((size_t)C * R));
         int rho = 0;

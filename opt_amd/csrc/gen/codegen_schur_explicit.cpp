@@ -223,6 +223,7 @@ void emit_schur_explicit(Ctx& cx, std::ostringstream& o) {
             std::ostringstream pre, body, decl, tail;
             Body b(cx, body, cx.nd_of(es));
             b.hoist_to(&pre, (int)k, (int)g);
+            if (cx.has_loss()) b.weight_at(cx.weight_at_q(sbk));
             for (int rs : rslots) {
                 decl << "        T";
                 for (int i = 0; i < CR; ++i)

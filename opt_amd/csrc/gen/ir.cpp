@@ -68,6 +68,12 @@ int Pool::coord(int dim, int off) {
     n.off[dim] = off;
     return intern(n);
 }
+int Pool::weight(int group) {
+    Node n;
+    n.op = Op::Weight;
+    n.i = group;
+    return intern(n);
+}
 
 double fold1(Op op, double a) {
     switch (op) {
@@ -325,7 +331,8 @@ int Pool::shift(int id, const int* s) {
         }
         case Op::Coord: r = coord(n.i, n.off[n.i] + s[n.i]); break;
         case Op::Const:
-        case Op::Param: r = id; break;
+        case Op::Param:
+        case Op::Weight: r = id; break;
         case Op::Select: r = select(shift(n.a, s), shift(n.b, s), shift(n.d, s)); break;
         case Op::Sample: r = sample(n.i, n.ch, shift(n.a, s), shift(n.b, s), n.off2[0], n.off2[1]); break;
         default:
@@ -353,6 +360,7 @@ std::string Pool::str(int id) const {
             o << "idx" << n.i;
             if (n.off[n.i]) o << (n.off[n.i] > 0 ? "+" : "") << n.off[n.i];
             break;
+        case Op::Weight: o << "W" << n.i; break;
         case Op::Select: o << "(" << str(n.a) << " ? " << str(n.b) << " : " << str(n.d) << ")"; break;
         case Op::Sample: o << "sample_I" << n.i << "[" << n.ch << "](" << str(n.a) << ", " << str(n.b) << ")"; break;
         default: {

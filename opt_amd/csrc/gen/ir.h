@@ -34,6 +34,8 @@ enum class Op : uint8_t {
     // names the cache images, so the ops above keep theirs
     Tan, Tanh, Sinh, Cosh, Asin, Acos, Atan, Asinh, Acosh, Log10,
     Atan2,    // the C library's atan2(a, b): the angle of the point (x = b, y = a)
+    Weight,   // RobustEnergy: loss group i's cached per-edge weight sqrt(rho'(s)), a constant of the
+              // linearisation (diff gives 0; the emitter loads it, codegen_body.cpp)
 };
 
 // op(a) / op(a, b) of constants, in double (constant folding; the value a cached
@@ -63,6 +65,7 @@ public:
     int read(int image, int ch, const int* off, int slot = -1, int graph = -1);
     int inbox(const int* lo, const int* hi);
     int coord(int dim, int off = 0);
+    int weight(int group);
     int un(Op op, int a);
     int bin(Op op, int a, int b);
     int select(int c, int a, int b);

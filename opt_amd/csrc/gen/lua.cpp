@@ -585,6 +585,9 @@ private:
     std::shared_ptr<Scope> globals_;
     std::vector<int> energy_terms_;   // scalar residual expressions, in Energy order
     std::vector<int> exclude_terms_;  // Exclude expressions, in call order
+    // RobustEnergy statements, in call order: GModel::loss[g] (kind and scale set at the call) and
+    // its scalar terms, classified by finish() after the Energy terms
+    std::vector<std::vector<int>> robust_terms_;
     std::vector<std::pair<int, int>> sample_cache_;   // cached Sample node (offset 0) -> its image
     int cache_samples(int e);
     int line_ = 0;
@@ -1305,6 +1308,31 @@ void Interp::install() {
             for (int c : as_expr(v)) energy_terms_.push_back(c);
         return VList{};
     });
+    def("RobustEnergy", [this](VList& a) {
+        GLossGroup L;
+        if (a.empty() || a[0].k != V::Str || (a[0].s != "huber" && a[0].s != "cauchy"))
+            err("RobustEnergy(kind, scale, term, ...): kind is \"huber\" or \"cauchy\"" +
+                (!a.empty() && a[0].k == V::Str ? " (got \"" + a[0].s + "\")" : std::string()));
+        L.kind = a[0].s == "huber" ? GLossGroup::Huber : GLossGroup::Cauchy;
+        if (a.size() >= 2 && a[1].k == V::Num) {
+            if (!(a[1].n > 0.0)) err("RobustEnergy: the scale must be positive (got " + numstr(a[1].n) + ")");
+            L.scale = a[1].n;
+        } else if (a.size() >= 2 && a[1].k == V::Expr && a[1].e.size() == 1 && P().at(a[1].e[0]).op == Op::Param &&
+                   m_->params[P().at(a[1].e[0]).i].type == "float") {
+            L.scale_param = P().at(a[1].e[0]).i;
+        } else {
+            err("RobustEnergy: the scale is a positive number or a float Param");
+        }
+        std::vector<int> terms;
+        for (size_t i = 2; i < a.size(); ++i)
+            for (int c : as_expr(a[i])) terms.push_back(c);
+        if (terms.empty()) err("RobustEnergy: no terms (a loss block needs at least one residual)");
+        if ((int)m_->loss.size() >= GModel::kMaxLossGroups)
+            err("RobustEnergy: more than " + std::to_string(GModel::kMaxLossGroups) + " loss groups in one energy");
+        m_->loss.push_back(L);
+        robust_terms_.push_back(terms);
+        return VList{};
+    });
     def("Result", [](VList&) { return VList{}; });
     def("ComputedArray", [this](VList& a) { return VList{computed_array(a)}; });
     def("ComputedImage", [this](VList& a) { return VList{computed_array(a)}; });
@@ -1628,7 +1656,13 @@ void Interp::finish() {
         m_->excludes.push_back({s, e});
         if (m_->exclude < 0) m_->exclude = e;
     }
-    for (int e : energy_terms_) {
+    // the Energy terms, then each RobustEnergy statement's (group >= 0)
+    std::vector<std::pair<int, int>> terms;
+    for (int e : energy_terms_) terms.push_back({e, -1});
+    for (size_t g = 0; g < robust_terms_.size(); ++g)
+        for (int e : robust_terms_[g]) terms.push_back({cache_samples(e), (int)g});
+    for (const auto& term : terms) {
+        const int e = term.first, group = term.second;
         GResidual r;
         bool any = false;
         int graph = -1;
@@ -1680,7 +1714,20 @@ void Interp::finish() {
         });
         if (!any) throw LuaError("residual must actually use some image");
         r.graph = graph;
-        if (graph < 0) {
+        if (group >= 0) {
+            // a loss block is an edge's: graph terms of one graph. The template is W f
+            GLossGroup& L = m_->loss[group];
+            const std::string nth = "RobustEnergy: term " + std::to_string(L.raw.size() + 1) + " of statement " +
+                                    std::to_string(group + 1);
+            if (graph < 0) throw LuaError(nth + " is a centred (non-graph) term (a loss block is one graph's edge)");
+            if (L.graph >= 0 && L.graph != graph)
+                throw LuaError(nth + " reads graph '" + m_->graphs[graph].name + "', the terms before it graph '" +
+                               m_->graphs[L.graph].name + "' (all terms of one statement are terms of the same graph)");
+            L.graph = graph;
+            L.raw.push_back(e);
+            L.residuals.push_back((int)m_->residuals.size());
+            r.expr = P().bin(Op::Mul, P().weight(group), e);
+        } else if (graph < 0) {
             // a centred residual is instantiated over the one space its reads lie over
             // (the reference's classifyexpression asserts a single IndexSpace per term)
             if (centred_imgs.size() > 1)

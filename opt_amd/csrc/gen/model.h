@@ -66,6 +66,21 @@ struct GBlockGroup {
     int entries() const { return C * (C + 1) / 2; }   // packed lower triangle
 };
 
+// RobustEnergy(kind, scale, term, ...): one loss block per edge of `graph` over the statement's
+// scalar residuals f_1..f_R, s = sum f_k^2. Its templates in GModel::residuals are the
+// weighted f~_k = W f_k (W: Pool::weight(group), the cached sqrt(rho'(s)) of the edge), so
+// every emitter that differentiates a residual gets the reweighted problem; `raw` keeps the
+// f_k for the kernels that need s and rho (gen_cost, gen_loss_weights).
+struct GLossGroup {
+    enum Kind { Huber = 0, Cauchy = 1 };
+    int graph = -1;
+    int kind = Huber;
+    double scale = 0.0;            // the constant a (scale_param < 0)
+    int scale_param = -1;          // GModel::params id of a float Param scale, re-read per evaluation
+    std::vector<int> residuals;    // ids in GModel::residuals (the weighted templates), statement order
+    std::vector<int> raw;          // the f_k, same order
+};
+
 struct GModel {
     Pool pool;
     std::vector<GDim> dims;
@@ -99,6 +114,14 @@ struct GModel {
     // is a block SpMV (codegen_normal.cpp); "matrix_free" / no statement: the gather apply. Turns
     // the block preconditioner on. The shapes this form takes: normal_refusal()
     bool normal_explicit = false;
+    std::vector<GLossGroup> loss;  // RobustEnergy statements, in order (at most kMaxLossGroups)
+    static constexpr int kMaxLossGroups = 4;
+    int loss_group_of(int residual) const {   // the group a residual template belongs to, -1 = plain
+        for (size_t g = 0; g < loss.size(); ++g)
+            for (int r : loss[g].residuals)
+                if (r == residual) return (int)g;
+        return -1;
+    }
     bool schur() const { return elim_space >= 0; }
     bool is_eliminated(int image) const {
         for (int k : eliminated)

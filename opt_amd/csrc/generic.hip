@@ -75,6 +75,10 @@ __global__ void incidence_count(const int* keys, int E, int* counts) {
 __global__ void incidence_gather(const int* slot, const int* geid, int E, int* out) {
     for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < E; q += gridDim.x * blockDim.x) out[q] = slot[geid[q]];
 }
+// pos[geid[q]] = q: where each edge sits in an incidence list (geid is a permutation of [0, E))
+__global__ void incidence_positions(const int* geid, int E, int* pos) {
+    for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < E; q += gridDim.x * blockDim.x) pos[geid[q]] = q;
+}
 __global__ void iota_kernel(int* v, int n) {
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) v[i] = i;
 }
@@ -137,6 +141,17 @@ bool generic_accepts(const std::string& text, ProblemSpec* spec, std::string* er
     for (auto& sp : m.spaces)
         if (sp.size() < 1 || sp.size() > 3) { *err = "index spaces must be 1-, 2- or 3-dimensional"; return false; }
     if (m.residuals.empty()) { *err = "no Energy terms"; return false; }
+    {   // RobustEnergy: one incidence-order weights array per (group, slot that carries its unknowns)
+        size_t arrays = 0;
+        for (auto& L : m.loss) {
+            std::vector<int> sl;
+            for (int ri : L.residuals)
+                for (int u : m.residuals[ri].unknowns)
+                    if (std::find(sl.begin(), sl.end(), m.pool.at(u).slot) == sl.end()) sl.push_back(m.pool.at(u).slot);
+            arrays += sl.size();
+        }
+        if (arrays > 16) { *err = "RobustEnergy: more than 16 (loss group, graph slot) weight arrays"; return false; }
+    }
     if (m.block_preconditioner)
         for (auto& g : m.block_groups())
             if (g.C > 8) {
@@ -205,6 +220,11 @@ bool generic_signature(const std::string& text, std::string* sig, bool* use_pre,
     if (m.schur()) s += "S" + std::to_string(m.elim_space) + ";";
     // ReducedSystem("explicit"): the reduced system's form ("implicit" is no statement)
     if (m.schur() && m.reduced_explicit) s += "RX;";
+    // RobustEnergy: per loss group its graph, kind and residual count (the scale is in the
+    // templates' W leaf only by group, so kind and count are named here)
+    for (auto& L : m.loss)
+        s += "L" + std::to_string(L.graph) + ":" + (L.kind == gen::GLossGroup::Huber ? "huber" : "cauchy") + ":" +
+             std::to_string(L.residuals.size()) + ";";
     *sig = s;
     if (use_pre) *use_pre = m.use_preconditioner;
     return true;
@@ -320,6 +340,16 @@ public:
                 OPT_HIP_CHECK(hipMemset(dimg_[i], 0, image_bytes(i)));
                 a_.img[i] = dimg_[i];
             }
+        // RobustEnergy: the cached weights, one value per edge in edge order per group and one
+        // per (group, slot) in that slot's incidence order (filled by gen_loss_weights)
+        for (size_t g = 0; g < m_.loss.size(); ++g) {
+            lwe_[g] = dmalloc(sizeof(T) * std::max(1, nedge_[m_.loss[g].graph]));
+            a_.lwe[g] = lwe_[g];
+        }
+        for (size_t i = 0; i < src_.loss_inc.size() && i < 16; ++i) {
+            lwq_[i] = dmalloc(sizeof(T) * std::max(1, nedge_[m_.loss[src_.loss_inc[i].first].graph]));
+            a_.lwq[i] = lwq_[i];
+        }
         if (opts_.host_buffers) {
             for (size_t i = 0; i < m_.images.size(); ++i)
                 if (!m_.images[i].internal) dimg_[i] = dmalloc(std::max<size_t>(1, image_bytes(i)));
@@ -334,6 +364,9 @@ public:
         for (int* p : dslot_) dfree(p);
         for (int k = 0; k < 16; ++k) { dfree(goff_[k]); dfree(geid_[k]); }
         for (int k = 0; k < 32; ++k) dfree(gnb_[k]);
+        for (void* p : lwe_) dfree(p);
+        for (void* p : lwq_) dfree(p);
+        for (int* p : lpos_) dfree(p);
         dfree(fp_scratch_);
         schur_explicit_release();
         if (mod_) (void)hipModuleUnload(mod_);
@@ -406,6 +439,11 @@ public:
                         : t == "uint" || t == "uint32" ? (double)*(const unsigned*)p
                                                        : (double)*(const float*)p;
         }
+        // a loss group's Param scale, as bound now (gen_loss_weights and gen_cost read it from prm)
+        for (auto& L : m_.loss)
+            if (L.scale_param >= 0 && !(a_.prm[L.scale_param] > 0.0))
+                throw PlanError("generic: RobustEnergy: the scale Param '" + m_.params[L.scale_param].name + "' is " +
+                                std::to_string(a_.prm[L.scale_param]) + " (a loss scale must be positive)");
         int sb = 0;
         for (size_t g = 0; g < m_.graphs.size(); ++g) {
             for (size_t k = 0; k < m_.graphs[g].slot_names.size(); ++k, ++sb) {
@@ -788,6 +826,42 @@ public:
         for (const void* q : {(const void*)sx_rowptr_, (const void*)sx_colind_, (const void*)sx_val_, (const void*)nx_longrow_})
             key->push_back((unsigned long long)(uintptr_t)q);
     }
+    // ---- robust losses (RobustEnergy; StencilPlan: HasLossWeights; gen/codegen.cpp emit_loss_weights) ----
+    // loss_weights caches w = sqrt(rho'(s)) per edge for the kernels of this linearisation: after
+    // every precompute (Init, update, revert, the stand-alone entry points) and at Step start,
+    // after the caches its residuals may read. eval_loss_rho1 writes rho'(s) of one group to the
+    // caller's array and leaves the caches alone.
+    bool has_loss() const { return src_.has_loss; }
+    void loss_weights(hipStream_t s) {
+        T* none = nullptr;
+        int all = -1;
+        launch(k_loss_weights_, s, {&a_, &none, &all});
+    }
+    int loss_groups(int max_groups, int* graph, int* residuals, int* kind) const {
+        for (size_t g = 0; g < m_.loss.size() && (int)g < max_groups; ++g) {
+            if (graph) graph[g] = m_.loss[g].graph;
+            if (residuals) residuals[g] = (int)m_.loss[g].residuals.size();
+            if (kind) kind[g] = m_.loss[g].kind;
+        }
+        return (int)m_.loss.size();
+    }
+    long long loss_group_edges(int group) const {
+        return group >= 0 && group < (int)m_.loss.size() ? nedge_[m_.loss[group].graph] : -1;
+    }
+    void eval_loss_rho1(int group, T* out, hipStream_t s) {
+        if (group < 0 || group >= (int)m_.loss.size())
+            throw PlanError("generic: OptAMD_EvalLossWeights: loss group " + std::to_string(group) + " of " +
+                            std::to_string(m_.loss.size()));
+        T* dst = out;
+        const size_t bytes = sizeof(T) * (size_t)nedge_[m_.loss[group].graph];
+        if (opts_.host_buffers) dst = (T*)dmalloc(std::max<size_t>(1, bytes));
+        launch(k_loss_weights_, s, {&a_, &dst, &group});
+        if (opts_.host_buffers) {
+            OPT_HIP_CHECK(hipMemcpyAsync(out, dst, bytes, hipMemcpyDeviceToHost, s));
+            OPT_HIP_CHECK(hipStreamSynchronize(s));
+            dfree(dst);
+        }
+    }
     void apply(const T* p, T* Ap, const T* dadd, const int* stop, ReduceSlot rs, hipStream_t s) {
         if (!src_.has_graph) {
             int finish = 1;
@@ -807,18 +881,19 @@ public:
     // materialized Jacobian (useMaterializedJTJ, csr.h): the generated saveJToCRS kernels
     // (none over several index spaces: -1, and dump_j refuses)
     long long jacobian_rows() const {
-        if (multi_) return -1;
+        if (multi_ || src_.has_loss) return -1;
         long long r = 0;
         for (auto& d : src_.dump) r += elements(d.graph) * d.rows;
         return r;
     }
     long long jacobian_nnz() const {
-        if (multi_) return -1;
+        if (multi_ || src_.has_loss) return -1;
         long long z = 0;
         for (auto& d : src_.dump) z += elements(d.graph) * d.nnz;
         return z;
     }
     void dump_j(int* rowPtr, int* colInd, T* val, hipStream_t s) {
+        if (src_.has_loss) throw PlanError("generic: no Jacobian assembly (OptAMD_EvalJacobian) for an energy with a RobustEnergy statement");
         if (multi_) throw PlanError("generic: no Jacobian assembly (OptAMD_EvalJacobian) for an energy over several index spaces");
         long long rb = 0, zb = 0;
         for (size_t i = 0; i < src_.dump.size(); ++i) {
@@ -958,6 +1033,7 @@ private:
                             std::make_pair(&k_schur_spmv_, "gen_schur_spmv")})
                 OPT_HIP_CHECK(hipModuleGetFunction(kv.first, mod_, kv.second));
         }
+        if (src_.has_loss) OPT_HIP_CHECK(hipModuleGetFunction(&k_loss_weights_, mod_, "gen_loss_weights"));
         if (src_.has_normal) {
             for (auto kv : {std::make_pair(&k_normal_eblk_, "gen_normal_eblk"), std::make_pair(&k_normal_assemble_, "gen_normal_assemble"),
                             std::make_pair(&k_normal_assemble_long_, "gen_normal_assemble_long"),
@@ -1087,6 +1163,7 @@ private:
             a_.geid[k] = geid_[k];
         }
         for (size_t i = 0; i < src_.nb_pairs.size() && i < 32; ++i) a_.gnb[i] = gnb_[i];
+        for (int k = 0; k < sb && k < 16; ++k) a_.lpos[k] = lpos_[k];
     }
     // GenArgs::gnb of every (slot k, other slot) pair whose incidence list was rebuilt:
     // the other slot's vertex of each incident edge, in the incidence order
@@ -1126,6 +1203,13 @@ private:
         hipLaunchKernelGGL(incidence_count, dim3(grid), dim3(256), 0, s, a_.slot[sb], E, goff_[sb]);
         size_t n2 = need;
         OPT_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp, n2, goff_[sb], goff_[sb], (int)nv + 1, s));
+        // RobustEnergy: the inverse of geid for the slots that carry a group's unknowns
+        for (auto& li : src_.loss_inc)
+            if (li.second == sb && !lpos_[sb]) lpos_[sb] = (int*)dmalloc(sizeof(int) * E);
+        if (lpos_[sb]) {
+            hipLaunchKernelGGL(incidence_positions, dim3(grid), dim3(256), 0, s, (const int*)geid_[sb], E, lpos_[sb]);
+            OPT_HIP_CHECK(hipGetLastError());
+        }
         OPT_HIP_CHECK(hipStreamSynchronize(s));
         dfree(tmp);
         dfree(keys);
@@ -1157,6 +1241,12 @@ private:
     int* goff_[16] = {};
     int* geid_[16] = {};
     int* gnb_[32] = {};
+    // RobustEnergy: weights in edge order per group, in incidence order per GenSource::loss_inc
+    // entry, and per slot the inverse of geid (rebuilt with it)
+    void* lwe_[4] = {};
+    void* lwq_[16] = {};
+    int* lpos_[16] = {};
+    hipFunction_t k_loss_weights_{};
     // grid of every generic kernel (all walk their work grid-stride); a register-strip apply
     // sets it to the blocks the chip holds at once (below), OPT_AMD_GEN_BLOCKS overrides
     int max_blocks_ = std::min(4096, std::max(8, env_int("OPT_AMD_GEN_BLOCKS", 2048)));
@@ -1201,6 +1291,7 @@ private:
 static_assert(HasBlockPre<GenericOp<float>>::value);   // the optional driver features this Op claims (stencil_plan.h)
 static_assert(HasSchur<GenericOp<float>>::value);
 static_assert(HasNormal<GenericOp<float>>::value);
+static_assert(HasLossWeights<GenericOp<float>>::value);
 static_assert(HasCaptureKey<GenericOp<float>>::value);
 static_assert(HasRefreshCaches<GenericOp<float>>::value);
 static_assert(HasSlabRefusal<GenericOp<float>>::value);
@@ -1246,6 +1337,11 @@ std::unique_ptr<Plan> make_generic_plan(const ProblemSpec& spec, const StateOpti
     if (m.normal_explicit && (opts.materialized || opts.fused_jtj)) {
         *err = "generic: no materialized Jacobian (useMaterializedJTJ / useFusedJTJ) with NormalMatrix(\"explicit\"): "
                "the plan forms J^T J itself";
+        return nullptr;
+    }
+    if (!m.loss.empty() && (opts.materialized || opts.fused_jtj)) {
+        *err = "generic: no materialized Jacobian (useMaterializedJTJ / useFusedJTJ) with RobustEnergy: the weights "
+               "are the matrix-free kernels'";
         return nullptr;
     }
     if (m.multi()) {
@@ -1333,6 +1429,16 @@ int generic_describe(const std::string& text, std::string* out) {
             dom += "}";
         }
         s += dom + " " + std::to_string(r.unknowns.size()) + " " + m.pool.str(r.expr) + "\n";
+    }
+    // RobustEnergy statements: "loss<g> graph<id> <kind> scale=<a | param name> residuals=<R>"
+    for (size_t g = 0; g < m.loss.size(); ++g) {
+        const gen::GLossGroup& L = m.loss[g];
+        char a[64];
+        snprintf(a, sizeof a, "%g", L.scale);
+        s += "loss" + std::to_string(g) + " graph" + std::to_string(L.graph) + " " +
+             (L.kind == gen::GLossGroup::Huber ? "huber" : "cauchy") + " scale=" +
+             (L.scale_param >= 0 ? "param " + m.params[L.scale_param].name : std::string(a)) + " residuals=" +
+             std::to_string(L.residuals.size()) + "\n";
     }
     *out = s;
     return (int)m.residuals.size();

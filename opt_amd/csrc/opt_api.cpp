@@ -256,6 +256,17 @@ int OptAMD_PlanEliminated(Opt_Plan* plan, int maxImages, int* eliminated) {
     if (!valid_plan(plan, "OptAMD_PlanEliminated")) return -1;
     return plan->impl->eliminated(maxImages, eliminated);
 }
+int OptAMD_PlanLossGroups(Opt_Plan* plan, int maxGroups, int* graph, int* residuals, int* kind) {
+    if (!valid_plan(plan, "OptAMD_PlanLossGroups")) return -1;
+    return plan->impl->loss_groups(maxGroups, graph, residuals, kind);
+}
+long long OptAMD_PlanLossGroupEdges(Opt_Plan* plan, int group) {
+    return valid_plan(plan, "OptAMD_PlanLossGroupEdges") ? plan->impl->loss_group_edges(group) : -1;
+}
+int OptAMD_EvalLossWeights(Opt_State* state, Opt_Plan* plan, void** params, int group, void* weights) {
+    if (!valid_state(state, "OptAMD_EvalLossWeights") || !valid_plan(plan, "OptAMD_EvalLossWeights") || !weights) return 1;
+    return guarded(plan, "OptAMD_EvalLossWeights", 1, [&] { return plan->impl->eval_loss_weights(params, group, weights); });
+}
 int OptAMD_ApplyReduced(Opt_State* state, Opt_Plan* plan, void** params, const void* p, void* Sp) {
     if (!valid_state(state, "OptAMD_ApplyReduced") || !valid_plan(plan, "OptAMD_ApplyReduced") || !p || !Sp) return 1;
     return guarded(plan, "OptAMD_ApplyReduced", 1, [&] { return plan->impl->apply_reduced(params, p, Sp); });

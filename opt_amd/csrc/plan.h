@@ -165,6 +165,20 @@ public:
             if (flag) flag[k] = 0;
         return n;
     }
+    // RobustEnergy (include/opt_amd.h): the plan's loss groups (0 on other plans), and rho'(s)
+    // per edge of one group at the bound unknowns (1 on a plan without the statement)
+    virtual int loss_groups(int max_groups, int* graph, int* residuals, int* kind) const {
+        (void)max_groups; (void)graph; (void)residuals; (void)kind;
+        return 0;
+    }
+    virtual long long loss_group_edges(int group) const {   // edges of the group's graph, -1 = no such group
+        (void)group;
+        return -1;
+    }
+    virtual int eval_loss_weights(void** params, int group, void* weights) {
+        (void)params; (void)group; (void)weights;
+        return 1;
+    }
     // Sp = S p, the Schur complement's product at the current unknowns (device vectors of
     // unknown_count() elements); 1 where the plan eliminates nothing.
     virtual int apply_reduced(void** params, const void* p, void* Sp) {

@@ -211,6 +211,14 @@ OPTAMD_OP_TRAIT(HasNormal, normal);
 // Ops that choose among several forms of their kernels (GenericOp: gather, LDS tiles, register
 // strips): std::string generated_forms() const, the forms this plan launches.
 OPTAMD_OP_TRAIT(HasGeneratedForms, generated_forms);
+
+// Ops with robust losses (GenericOp for RobustEnergy): has_loss() says whether this energy has
+// the statement. loss_weights(s) caches one weight sqrt(rho'(s)) per edge and loss group at the
+// bound unknowns; every kernel of the linear system reads it. It follows precompute (Init, after
+// update, after revert, the stand-alone entry points) and the per-Step refresh, after both:
+// arrays, Params and unknowns may change between Steps. Cost and model cost evaluate rho
+// themselves. loss_groups / eval_loss_rho1: OptAMD_PlanLossGroups / OptAMD_EvalLossWeights.
+OPTAMD_OP_TRAIT(HasLossWeights, loss_weights);
 #undef OPTAMD_OP_TRAIT
 
 // r -= Ap (and b = r, LM): the reduced right-hand side from Ap = E M^-1 b_e
@@ -321,6 +329,7 @@ public:
         if constexpr (HasRefreshCaches<Op>::value) {
             if (op_->refresh_caches(stream_)) exchange_computed();
         }
+        loss_weights();
         const int Lit = std::max(0, sp_.lIterations);
         red_.ensure(std::max(op_->stencil_blocks(), 4096), 4, kScBase + kSlots * (Lit + 2));
         OPT_HIP_CHECK(hipMemsetAsync(stop_, 0, 64, stream_));
@@ -665,6 +674,27 @@ public:
             return 0;
         }
         return Plan::normal_matrix(params, rowPtr, colInd, val);
+    }
+    int loss_groups(int max_groups, int* graph, int* residuals, int* kind) const override {
+        if constexpr (HasLossWeights<Op>::value) return op_->loss_groups(max_groups, graph, residuals, kind);
+        return 0;
+    }
+    long long loss_group_edges(int group) const override {
+        if constexpr (HasLossWeights<Op>::value) return op_->loss_group_edges(group);
+        return -1;
+    }
+    // rho'(s) per edge of one loss group at the bound unknowns; 1 on a plan without the statement
+    int eval_loss_weights(void** params, int group, void* weights) override {
+        if constexpr (HasLossWeights<Op>::value) {
+            if (!op_->has_loss()) return 1;
+            begin_call();
+            prepare(params);
+            op_->eval_loss_rho1(group, (T*)weights, stream_);
+            OPT_HIP_CHECK(hipStreamSynchronize(stream_));
+            end_call();
+            return 0;
+        }
+        return Plan::eval_loss_weights(params, group, weights);
     }
     int preconditioner_blocks(int max_images, int* group, int* first_row) const override {
         if constexpr (HasBlockPre<Op>::value)
@@ -1139,10 +1169,19 @@ private:
         exchange_unknowns();
         op_->precompute(stream_);
         exchange_computed();
+        loss_weights();
     }
     void precompute() {
         tbegin("precompute"); op_->precompute(stream_); tend();
         exchange_computed();
+        loss_weights();
+    }
+    // robust losses: the per-edge weights of this linearisation (HasLossWeights)
+    void loss_weights() {
+        if constexpr (HasLossWeights<Op>::value)
+            if (op_->has_loss()) {
+                tbegin("gen_loss_weights"); op_->loss_weights(stream_); tend();
+            }
     }
 
     bool distributed() const { return comm_ && comm_->size() > 1; }

@@ -55,6 +55,16 @@ int main(int argc, char** argv) {
         printf("// dump[%zu]: graph=%d rows=%d nnz=%d\n", i, gs.dump[i].graph, gs.dump[i].rows, gs.dump[i].nnz);
     for (size_t i = 0; i < gs.nb_pairs.size(); ++i)
         printf("// nb_pairs[%zu]: %d %d\n", i, gs.nb_pairs[i].first, gs.nb_pairs[i].second);
+    // RobustEnergy statements (files without one print nothing here)
+    for (size_t g = 0; g < m.loss.size(); ++g) {
+        const optamd::gen::GLossGroup& L = m.loss[g];
+        printf("// loss[%zu]: graph=%d kind=%s residuals=%zu scale=", g, L.graph, L.kind == L.Huber ? "huber" : "cauchy",
+               L.residuals.size());
+        if (L.scale_param >= 0) printf("param %d\n", L.scale_param);
+        else printf("%.17g\n", L.scale);
+    }
+    for (size_t i = 0; i < gs.loss_inc.size(); ++i)
+        printf("// loss_inc[%zu]: group=%d slot=%d\n", i, gs.loss_inc[i].first, gs.loss_inc[i].second);
     for (size_t i = declared; i < m.images.size(); ++i) {
         const optamd::gen::GImage& im = m.images[i];
         std::string dims;
