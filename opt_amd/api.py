@@ -381,29 +381,39 @@ class OptSolver:
     def reduced_matrix_shape(self):
         """(block rows, block dimension, blocks) of the explicitly formed S once the graphs
         are bound (OptAMD_PlanReducedMatrixShape); None on any other plan, or before."""
-        rows, dim, nnzb = ctypes.c_longlong(), ctypes.c_int(), ctypes.c_longlong()
-        k = self.lib.OptAMD_PlanReducedMatrixShape(self.plan, ctypes.byref(rows), ctypes.byref(dim), ctypes.byref(nnzb))
-        if k < 0:
-            raise OptError("OptAMD_PlanReducedMatrixShape failed")
-        return (rows.value, dim.value, nnzb.value) if k == 1 else None
+        return self._matrix_shape("OptAMD_PlanReducedMatrixShape")
 
     def reduced_matrix(self, problem_params):
         """S = B - E M^-1 E^T assembled at the bound unknowns, in block-CSR (OptAMD_ReducedMatrix
         on a plan whose energy has ReducedSystem("explicit")): (rowPtr, colInd, val[nnzb, C, C])
         as torch tensors on the plan's device."""
+        return self._matrix("OptAMD_ReducedMatrix", self.reduced_matrix_shape, problem_params,
+                            "the plan has no explicit reduced system")
+
+    def _matrix_shape(self, fn):
+        rows, dim, nnzb = ctypes.c_longlong(), ctypes.c_int(), ctypes.c_longlong()
+        k = getattr(self.lib, fn)(self.plan, ctypes.byref(rows), ctypes.byref(dim), ctypes.byref(nnzb))
+        if k < 0:
+            raise OptError(fn + " failed")
+        return (rows.value, dim.value, nnzb.value) if k == 1 else None
+
+    def _matrix(self, fn, shape, problem_params, missing):
+        """The assembled block-CSR matrix of an explicit plan: one call of `fn` binds and builds the
+        pattern, `shape` sizes the tensors, a second call fills them."""
         import torch
+        call = getattr(self.lib, fn)
         pk = ParamPack(problem_params)
-        if self.lib.OptAMD_ReducedMatrix(self.plan, pk.ptr, None, None, None):
+        if call(self.plan, pk.ptr, None, None, None):
             self._raise_plan_error()
-            raise OptError("OptAMD_ReducedMatrix failed (the plan has no explicit reduced system)")
-        rows, dim, nnzb = self.reduced_matrix_shape()
+            raise OptError(f"{fn} failed ({missing})")
+        rows, dim, nnzb = shape()
         row_ptr = torch.empty(rows + 1, dtype=torch.int32, device="cuda")
         col_ind = torch.empty(max(nnzb, 1), dtype=torch.int32, device="cuda")
         val = torch.empty((max(nnzb, 1), dim, dim), dtype=torch.float64 if self.double_precision else torch.float32,
                           device="cuda")
-        if self.lib.OptAMD_ReducedMatrix(self.plan, pk.ptr, _ptr(row_ptr), _ptr(col_ind), _ptr(val)):
+        if call(self.plan, pk.ptr, _ptr(row_ptr), _ptr(col_ind), _ptr(val)):
             self._raise_plan_error()
-            raise OptError("OptAMD_ReducedMatrix failed")
+            raise OptError(fn + " failed")
         return row_ptr, col_ind[:nnzb], val[:nnzb]
 
     def symbolic_info(self):
@@ -419,30 +429,14 @@ class OptSolver:
     def normal_matrix_shape(self):
         """(block rows, block dimension, blocks) of the explicitly formed H = J^T J once the
         graphs are bound (OptAMD_PlanNormalMatrixShape); None on any other plan, or before."""
-        rows, dim, nnzb = ctypes.c_longlong(), ctypes.c_int(), ctypes.c_longlong()
-        k = self.lib.OptAMD_PlanNormalMatrixShape(self.plan, ctypes.byref(rows), ctypes.byref(dim), ctypes.byref(nnzb))
-        if k < 0:
-            raise OptError("OptAMD_PlanNormalMatrixShape failed")
-        return (rows.value, dim.value, nnzb.value) if k == 1 else None
+        return self._matrix_shape("OptAMD_PlanNormalMatrixShape")
 
     def normal_matrix(self, problem_params):
         """H = J^T J assembled at the bound unknowns, in block-CSR (OptAMD_NormalMatrix on a plan
         whose energy has NormalMatrix("explicit")): (rowPtr, colInd, val[nnzb, C, C]) as torch
         tensors on the plan's device."""
-        import torch
-        pk = ParamPack(problem_params)
-        if self.lib.OptAMD_NormalMatrix(self.plan, pk.ptr, None, None, None):
-            self._raise_plan_error()
-            raise OptError("OptAMD_NormalMatrix failed (the plan has no explicit normal matrix)")
-        rows, dim, nnzb = self.normal_matrix_shape()
-        row_ptr = torch.empty(rows + 1, dtype=torch.int32, device="cuda")
-        col_ind = torch.empty(max(nnzb, 1), dtype=torch.int32, device="cuda")
-        val = torch.empty((max(nnzb, 1), dim, dim), dtype=torch.float64 if self.double_precision else torch.float32,
-                          device="cuda")
-        if self.lib.OptAMD_NormalMatrix(self.plan, pk.ptr, _ptr(row_ptr), _ptr(col_ind), _ptr(val)):
-            self._raise_plan_error()
-            raise OptError("OptAMD_NormalMatrix failed")
-        return row_ptr, col_ind[:nnzb], val[:nnzb]
+        return self._matrix("OptAMD_NormalMatrix", self.normal_matrix_shape, problem_params,
+                            "the plan has no explicit normal matrix")
 
     def eval_cost(self, problem_params) -> float:
         pk = ParamPack(problem_params)

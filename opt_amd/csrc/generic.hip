@@ -18,10 +18,9 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include "explicit_matrix.h"
 #include "gen/codegen.h"
 #include "graph_util.h"
-#include "schur_pattern.h"
-#include "schur_pattern_dev.h"
 #include "stencil_plan.h"
 
 namespace optamd {
@@ -368,7 +367,6 @@ public:
         for (void* p : lwq_) dfree(p);
         for (int* p : lpos_) dfree(p);
         dfree(fp_scratch_);
-        schur_explicit_release();
         if (mod_) (void)hipModuleUnload(mod_);
     }
 
@@ -595,131 +593,34 @@ public:
     void schur_apply(const T* p, T* Ap, const T* dadd, const int* stop, ReduceSlot rs, hipStream_t s) {
         launch(k_schur_apply_, s, {&a_, &p, &w_, &Ap, &dadd, &stop, &rs});
     }
-    // ---- the explicitly formed S (ReducedSystem("explicit"); gen/codegen_schur_explicit.cpp) ----
-    // Symbolic phase (device, schur_pattern_dev.hip; host, schur_pattern.h, under OPT_AMD_SYMBOLIC=host
-    // or where the device form's temporaries do not fit): block-CSR pattern and per-block pair lists, built
-    // from the vertex arrays at the first use and again when the graphs were re-wired. Numeric
-    // phase, once per Step between schur_rhs (M_e^-1 in blk) and block_init (which inverts B_r
-    // in place): schur_eblk writes W_q, Y_q per edge instance, schur_assemble sums the blocks.
-    // schur_spmv then is gen_schur_apply's contract on the assembled matrix.
-    bool schur_explicit() const { return src_.has_schur_explicit; }
-    bool schur_symbolic_stale() const { return !sx_rowptr_ || sx_generation_ != topology_generation_; }
-    void schur_symbolic(hipStream_t s) {
-        if (!schur_symbolic_stale()) return;
-        schur_explicit_release();   // the old wiring's buffers first: both need not fit together
-        if (src_.schur_lists.size() > 16) throw PlanError("generic: ReducedSystem(\"explicit\"): more than 16 instance lists");
-        const size_t cw = (size_t)src_.schur_cr * src_.schur_ce, cc = (size_t)src_.schur_cr * src_.schur_cr;
-        bool built = false;
-        if (symbolic_mode_ != kSymbolicHost) {   // the lists in place, in the eliminated slots' incidence order
-            std::vector<SchurListDev> dl;
-            long long nq = 0;
-            for (auto& l : src_.schur_lists) {
-                dl.push_back({a_.slot[l.eslot], a_.slot[l.rslot], geid_[l.eslot], nedge_[l.graph], 0});
-                nq += nedge_[l.graph];
-            }
-            built = symbolic_device(snpix_[m_.elim_space], snpix_[src_.schur_rspace], dl, false, "explicit Schur complement", 0,
-                                    (long long)(2 * cw * sizeof(T)) * nq, s);
+    // ---- the assembled matrix (ReducedSystem("explicit"): S; NormalMatrix("explicit"): H = J^T J;
+    // StencilPlan: HasExplicitMatrix; explicit_matrix.h; gen/codegen_schur_explicit.cpp, codegen_normal.cpp) ----
+    // A file has at most one of the two statements: matrix_form() says which. Symbolic phase:
+    // block-CSR pattern, per-block pair lists and the long blocks / rows, built from the vertex
+    // arrays at the first use and again when the graphs were re-wired. Numeric phase, once per
+    // Step before block_init inverts the retained blocks in place — for S after schur_rhs (M_e^-1
+    // in blk), for H after jtf (the diagonal blocks in blk): matrix_eblk writes W_q, Y_q (S) or
+    // G_q (H) per edge instance, matrix_assemble sums the blocks. matrix_spmv then is
+    // gen_schur_apply's / apply's contract on the assembled matrix.
+    MatrixForm matrix_form() const {
+        return src_.has_schur_explicit ? MatrixForm::Schur : src_.has_normal ? MatrixForm::Normal : MatrixForm::None;
+    }
+    bool matrix_symbolic_stale() const { return xm_.stale(topology_generation_); }
+    void matrix_symbolic(hipStream_t s) {
+        if (!matrix_symbolic_stale()) return;
+        std::vector<SchurListDev> lists;
+        if (src_.has_schur_explicit) {   // the lists in the eliminated slots' incidence order
+            if (src_.schur_lists.size() > 16) throw PlanError("generic: ReducedSystem(\"explicit\"): more than 16 instance lists");
+            for (auto& l : src_.schur_lists)
+                lists.push_back({a_.slot[l.eslot], a_.slot[l.rslot], geid_[l.eslot], nedge_[l.graph], 0});
+            xm_.build({"explicit Schur complement", false, src_.schur_cr, src_.schur_cr * src_.schur_ce, 2, 0},
+                      snpix_[m_.elim_space], snpix_[src_.schur_rspace], lists, topology_generation_, s);
+            return;
         }
-        if (!built) schur_symbolic_host(s);
-        sx_val_ = (T*)dmalloc(sizeof(T) * std::max<size_t>(1, cc * sx_nnzb_));
-        sx_w_ = (T*)dmalloc(sizeof(T) * std::max<size_t>(1, cw * sx_nq_));
-        sx_y_ = (T*)dmalloc(sizeof(T) * std::max<size_t>(1, cw * sx_nq_));
-        sx_generation_ = topology_generation_;
-    }
-    // the host builder (schur_pattern.h): the slot arrays down, the pattern up
-    void schur_symbolic_host(hipStream_t s) {
-        std::map<int, std::vector<int>> host;   // GenArgs::slot index -> its vertices
-        std::vector<SchurList> lists;
-        for (auto& l : src_.schur_lists)
-            for (int sb : {l.eslot, l.rslot})
-                if (!host.count(sb)) {
-                    host[sb].resize(std::max(1, nedge_[l.graph]));
-                    OPT_HIP_CHECK(hipMemcpyAsync(host[sb].data(), a_.slot[sb], sizeof(int) * nedge_[l.graph],
-                                                 hipMemcpyDeviceToHost, s));
-                }
-        OPT_HIP_CHECK(hipStreamSynchronize(s));
-        for (auto& l : src_.schur_lists) lists.push_back({host[l.eslot].data(), host[l.rslot].data(), nedge_[l.graph]});
-        SchurPattern P;
-        try {
-            schur_pattern_build(snpix_[m_.elim_space], snpix_[src_.schur_rspace], lists, &P);
-        } catch (const std::length_error& e) {
-            throw PlanError(std::string("generic: ") + e.what());
-        }
-        for (size_t l = 0; l < P.base.size(); ++l) sx_qb_.b[l] = P.base[l];
-        sx_nnzb_ = P.n_blocks();
-        sx_npairs_ = P.n_pairs();
-        sx_nq_ = P.n_instances;
-        auto up = [&](const std::vector<int>& v) {
-            int* d = (int*)dmalloc(sizeof(int) * std::max<size_t>(1, v.size()));
-            if (!v.empty()) OPT_HIP_CHECK(hipMemcpyAsync(d, v.data(), sizeof(int) * v.size(), hipMemcpyHostToDevice, s));
-            return d;
-        };
-        sx_rowptr_ = up(P.rowPtr);
-        sx_colind_ = up(P.colInd);
-        sx_blkrow_ = up(P.blkRow);
-        sx_pairptr_ = up(P.pairPtr);
-        sx_pairs_ = up(P.pairs);
-        std::vector<int> lng;   // blocks gen_schur_assemble leaves to gen_schur_assemble_long
-        for (long long b = 0; b < sx_nnzb_; ++b)
-            if (P.pairPtr[b + 1] - P.pairPtr[b] > gen::kSchurLongPairs) lng.push_back((int)b);
-        sx_nlong_ = (int)lng.size();
-        sx_long_ = up(lng);
-        OPT_HIP_CHECK(hipStreamSynchronize(s));   // (the host vectors go out of scope)
-        symbolic_host_info();
-    }
-    void schur_eblk(hipStream_t s) { launch(k_schur_eblk_, s, {&a_, &blk_, &sx_w_, &sx_y_, &sx_qb_}); }
-    void schur_assemble(hipStream_t s) {
-        const int nnzb = (int)sx_nnzb_;
-        const int grid = (int)std::max<long long>(1, std::min<long long>((sx_nnzb_ + 3) / 4, 1 << 18));
-        launch_grid(k_schur_assemble_, grid, s, {&a_, &blk_, &sx_w_, &sx_y_, &sx_blkrow_, &sx_colind_, &sx_pairptr_, &sx_pairs_,
-                                                 &sx_val_, &nnzb});
-        if (sx_nlong_ > 0)
-            launch_grid(k_schur_assemble_long_, std::min(sx_nlong_, 1 << 16), s,
-                        {&a_, &blk_, &sx_w_, &sx_y_, &sx_blkrow_, &sx_colind_, &sx_pairptr_, &sx_pairs_, &sx_val_, &sx_long_,
-                         &sx_nlong_});
-    }
-    void schur_spmv(const T* p, T* Ap, const T* dadd, const int* stop, ReduceSlot rs, hipStream_t s) {
-        launch(k_schur_spmv_, s, {&a_, &sx_rowptr_, &sx_colind_, &sx_val_, &p, &Ap, &dadd, &stop, &rs});
-    }
-    // block rows, block dimension, blocks; false before the first symbolic phase
-    bool schur_matrix_shape(long long* rows, int* dim, long long* nnzb) const {
-        if (!src_.has_schur_explicit || !sx_rowptr_) return false;
-        if (rows) *rows = snpix_[src_.schur_rspace];
-        if (dim) *dim = src_.schur_cr;
-        if (nnzb) *nnzb = sx_nnzb_;
-        return true;
-    }
-    long long schur_matrix_pairs() const { return sx_npairs_; }
-    // what the last symbolic phase of S or H did (OptAMD_PlanSymbolicInfo); empty before the first
-    const std::string& symbolic_info() const { return sym_info_; }
-    void schur_matrix_copy(int* rowPtr, int* colInd, T* val, hipStream_t s) {
-        const long long nR = snpix_[src_.schur_rspace];
-        OPT_HIP_CHECK(hipMemcpyAsync(rowPtr, sx_rowptr_, sizeof(int) * (nR + 1), hipMemcpyDefault, s));
-        OPT_HIP_CHECK(hipMemcpyAsync(colInd, sx_colind_, sizeof(int) * sx_nnzb_, hipMemcpyDefault, s));
-        OPT_HIP_CHECK(hipMemcpyAsync(val, sx_val_, sizeof(T) * sx_nnzb_ * src_.schur_cr * src_.schur_cr, hipMemcpyDefault, s));
-    }
-    // the buffers the captured PCG loop's SpMV bakes in (StencilPlan::pcg_graph_begin)
-    void schur_explicit_key(std::vector<unsigned long long>* key) const {
-        for (const void* q : {(const void*)sx_rowptr_, (const void*)sx_colind_, (const void*)sx_val_})
-            key->push_back((unsigned long long)(uintptr_t)q);
-    }
-    // ---- the explicitly formed H = J^T J (NormalMatrix("explicit"); StencilPlan: HasNormal;
-    // gen/codegen_normal.cpp) ----
-    // Symbolic phase (the same two builders with the edge in the eliminated vertex's place):
-    // block-CSR pattern, per-block lists of instance pairs and the long rows, built from the
-    // vertex arrays at the first use and again when the graphs were re-wired. Numeric phase, once
-    // per Step between jtf (the diagonal blocks in blk) and block_init (which inverts them in
-    // place): normal_eblk writes G_q per edge instance, normal_assemble sums the blocks.
-    // normal_spmv then is apply's contract on the assembled matrix. The buffers are the
-    // explicit Schur complement's (sx_*): a file has one of the two statements.
-    bool normal() const { return src_.has_normal; }
-    bool normal_symbolic_stale() const { return !sx_rowptr_ || sx_generation_ != topology_generation_; }
-    void normal_symbolic(hipStream_t s) {
-        if (!normal_symbolic_stale()) return;
-        schur_explicit_release();   // the old wiring's buffers first: both need not fit together
         if (src_.normal_lists.size() > 16) throw PlanError("generic: NormalMatrix(\"explicit\"): more than 16 instance lists");
         // the edges of the graphs with lists, numbered graph after graph: edge e of graph g is
-        // "eliminated vertex" ebase[g] + e, and its instance in a list sits at position e
+        // "eliminated vertex" ebase[g] + e, and its instance in a list sits at position e (the
+        // edge is the vertex, the order the identity)
         long long ebase[4] = {0, 0, 0, 0}, ne = 0;
         for (size_t g = 0; g < m_.graphs.size() && g < 4; ++g) {
             bool used = false;
@@ -727,105 +628,36 @@ public:
             ebase[g] = ne;
             if (used) ne += nedge_[g];
         }
-        const long long nR = pixels_of(groups_[0].images[0]);
-        const size_t cw = (size_t)src_.normal_c * src_.normal_r, cc = (size_t)src_.normal_c * src_.normal_c;
-        bool built = false;
-        if (symbolic_mode_ != kSymbolicHost) {   // the lists in place: the edge is the vertex, the order the identity
-            std::vector<SchurListDev> dl;
-            long long nq = 0;
-            for (auto& L : src_.normal_lists) {
-                dl.push_back({nullptr, a_.slot[L.slot], nullptr, nedge_[L.graph], ebase[L.graph]});
-                nq += nedge_[L.graph];
-            }
-            built = symbolic_device(ne, nR, dl, true, "NormalMatrix(\"explicit\")", gen::kNormalLongRow,
-                                    (long long)(cw * sizeof(T)) * nq, s);
-        }
-        if (!built) normal_symbolic_host(ebase, ne, nR, s);
-        sx_val_ = (T*)dmalloc(sizeof(T) * std::max<size_t>(1, cc * sx_nnzb_));
-        sx_w_ = (T*)dmalloc(sizeof(T) * std::max<size_t>(1, cw * sx_nq_));
-        sx_generation_ = topology_generation_;
+        for (auto& l : src_.normal_lists) lists.push_back({nullptr, a_.slot[l.slot], nullptr, nedge_[l.graph], ebase[l.graph]});
+        xm_.build({"NormalMatrix(\"explicit\")", true, src_.normal_c, src_.normal_c * src_.normal_r, 1, gen::kNormalLongRow},
+                  ne, pixels_of(groups_[0].images[0]), lists, topology_generation_, s);
     }
-    // the host builder (schur_pattern.h): the slot arrays down, the pattern and the long lists up
-    void normal_symbolic_host(const long long* ebase, long long ne, long long nR, hipStream_t s) {
-        std::vector<std::vector<int>> host(src_.normal_lists.size()), ids(src_.normal_lists.size());
-        for (size_t l = 0; l < src_.normal_lists.size(); ++l) {
-            const auto& L = src_.normal_lists[l];
-            host[l].resize(std::max(1, nedge_[L.graph]));
-            OPT_HIP_CHECK(hipMemcpyAsync(host[l].data(), a_.slot[L.slot], sizeof(int) * nedge_[L.graph], hipMemcpyDeviceToHost, s));
-            ids[l].resize(std::max(1, nedge_[L.graph]));
-            for (int e = 0; e < nedge_[L.graph]; ++e) ids[l][e] = (int)(ebase[L.graph] + e);
-        }
-        OPT_HIP_CHECK(hipStreamSynchronize(s));
-        std::vector<SchurList> lists;
-        for (size_t l = 0; l < src_.normal_lists.size(); ++l)
-            lists.push_back({ids[l].data(), host[l].data(), nedge_[src_.normal_lists[l].graph]});
-        SchurPattern P;
-        try {
-            schur_pattern_build(ne, nR, lists, &P, true, "NormalMatrix(\"explicit\")");
-        } catch (const std::length_error& e) {
-            throw PlanError(std::string("generic: ") + e.what());
-        }
-        for (size_t l = 0; l < P.base.size(); ++l) sx_qb_.b[l] = P.base[l];
-        sx_nnzb_ = P.n_blocks();
-        sx_npairs_ = P.n_pairs();
-        sx_nq_ = P.n_instances;
-        auto up = [&](const std::vector<int>& v) {
-            int* d = (int*)dmalloc(sizeof(int) * std::max<size_t>(1, v.size()));
-            if (!v.empty()) OPT_HIP_CHECK(hipMemcpyAsync(d, v.data(), sizeof(int) * v.size(), hipMemcpyHostToDevice, s));
-            return d;
-        };
-        sx_rowptr_ = up(P.rowPtr);
-        sx_colind_ = up(P.colInd);
-        sx_blkrow_ = up(P.blkRow);
-        sx_pairptr_ = up(P.pairPtr);
-        sx_pairs_ = up(P.pairs);
-        std::vector<int> lng, lrow;   // blocks left to gen_normal_assemble_long, rows to the SpMV's workgroup form
-        for (long long b = 0; b < sx_nnzb_; ++b)
-            if (P.pairPtr[b + 1] - P.pairPtr[b] > gen::kSchurLongPairs) lng.push_back((int)b);
-        for (long long r = 0; r < nR; ++r)
-            if (P.rowPtr[r + 1] - P.rowPtr[r] > gen::kNormalLongRow) lrow.push_back((int)r);
-        sx_nlong_ = (int)lng.size();
-        sx_long_ = up(lng);
-        nx_nlongrow_ = (int)lrow.size();
-        nx_longrow_ = up(lrow);
-        OPT_HIP_CHECK(hipStreamSynchronize(s));   // (the host vectors go out of scope)
-        symbolic_host_info();
+    void matrix_eblk(hipStream_t s) {
+        const auto& m = xm_.buffers();
+        if (src_.has_normal) launch(k_mx_eblk_, s, {&a_, &m.inst[0], &m.qbase});
+        else launch(k_mx_eblk_, s, {&a_, &blk_, &m.inst[0], &m.inst[1], &m.qbase});
     }
-    void normal_eblk(hipStream_t s) { launch(k_normal_eblk_, s, {&a_, &sx_w_, &sx_qb_}); }
-    void normal_assemble(hipStream_t s) {
-        const int nnzb = (int)sx_nnzb_;
-        const long long per_wg = 4 * (64 / (src_.normal_c * src_.normal_c));   // blocks per workgroup (the packed form)
-        const int grid = (int)std::max<long long>(1, std::min<long long>((sx_nnzb_ + per_wg - 1) / per_wg, 1 << 18));
-        launch_grid(k_normal_assemble_, grid, s, {&a_, &blk_, &sx_w_, &sx_w_, &sx_blkrow_, &sx_colind_, &sx_pairptr_, &sx_pairs_,
-                                                  &sx_val_, &nnzb});
-        if (sx_nlong_ > 0)
-            launch_grid(k_normal_assemble_long_, std::min(sx_nlong_, 1 << 16), s,
-                        {&a_, &blk_, &sx_w_, &sx_w_, &sx_blkrow_, &sx_colind_, &sx_pairptr_, &sx_pairs_, &sx_val_, &sx_long_,
-                         &sx_nlong_});
+    void matrix_assemble(hipStream_t s) {
+        const auto& m = xm_.buffers();
+        // blocks per workgroup: 4, in H's packed form 4 per 64 / C^2 lanes; H's kernels take G_q as W_q and Y_q
+        const long long per_wg = src_.has_normal ? 4 * (64 / (src_.normal_c * src_.normal_c)) : 4;
+        T* const* yq = src_.has_normal ? &m.inst[0] : &m.inst[1];
+        const int nnzb = (int)m.nnzb;
+        const int grid = (int)std::max<long long>(1, std::min<long long>((m.nnzb + per_wg - 1) / per_wg, 1 << 18));
+        launch_grid(k_mx_assemble_, grid, s, {&a_, &blk_, &m.inst[0], yq, &m.blkRow, &m.colInd, &m.pairPtr, &m.pairs, &m.val, &nnzb});
+        if (m.nLong > 0)
+            launch_grid(k_mx_assemble_long_, std::min(m.nLong, 1 << 16), s,
+                        {&a_, &blk_, &m.inst[0], yq, &m.blkRow, &m.colInd, &m.pairPtr, &m.pairs, &m.val, &m.longBlk, &m.nLong});
     }
-    void normal_spmv(const T* p, T* Ap, const T* dadd, const int* stop, ReduceSlot rs, hipStream_t s) {
-        launch(k_normal_spmv_, s, {&a_, &sx_rowptr_, &sx_colind_, &sx_val_, &p, &Ap, &dadd, &stop, &rs, &nx_longrow_, &nx_nlongrow_});
+    void matrix_spmv(const T* p, T* Ap, const T* dadd, const int* stop, ReduceSlot rs, hipStream_t s) {
+        const auto& m = xm_.buffers();
+        if (src_.has_normal) launch(k_mx_spmv_, s, {&a_, &m.rowPtr, &m.colInd, &m.val, &p, &Ap, &dadd, &stop, &rs, &m.longRow, &m.nLongRow});
+        else launch(k_mx_spmv_, s, {&a_, &m.rowPtr, &m.colInd, &m.val, &p, &Ap, &dadd, &stop, &rs});
     }
-    // block rows, block dimension, blocks; false before the first symbolic phase
-    bool normal_matrix_shape(long long* rows, int* dim, long long* nnzb) const {
-        if (!src_.has_normal || !sx_rowptr_) return false;
-        if (rows) *rows = pixels_of(groups_[0].images[0]);
-        if (dim) *dim = src_.normal_c;
-        if (nnzb) *nnzb = sx_nnzb_;
-        return true;
-    }
-    long long normal_matrix_pairs() const { return sx_npairs_; }
-    void normal_matrix_copy(int* rowPtr, int* colInd, T* val, hipStream_t s) {
-        const long long nR = pixels_of(groups_[0].images[0]);
-        OPT_HIP_CHECK(hipMemcpyAsync(rowPtr, sx_rowptr_, sizeof(int) * (nR + 1), hipMemcpyDefault, s));
-        OPT_HIP_CHECK(hipMemcpyAsync(colInd, sx_colind_, sizeof(int) * sx_nnzb_, hipMemcpyDefault, s));
-        OPT_HIP_CHECK(hipMemcpyAsync(val, sx_val_, sizeof(T) * sx_nnzb_ * src_.normal_c * src_.normal_c, hipMemcpyDefault, s));
-    }
-    // the buffers the captured PCG loop's SpMV bakes in (StencilPlan::pcg_graph_begin)
-    void normal_key(std::vector<unsigned long long>* key) const {
-        for (const void* q : {(const void*)sx_rowptr_, (const void*)sx_colind_, (const void*)sx_val_, (const void*)nx_longrow_})
-            key->push_back((unsigned long long)(uintptr_t)q);
-    }
+    bool matrix_shape(long long* rows, int* dim, long long* nnzb) const { return xm_.shape(rows, dim, nnzb); }
+    void matrix_copy(int* rowPtr, int* colInd, T* val, hipStream_t s) { xm_.copy_out(rowPtr, colInd, val, s); }
+    void matrix_key(std::vector<unsigned long long>* key) const { xm_.capture_key(key); }
+    const std::string& symbolic_info() const { return xm_.info(); }
     // ---- robust losses (RobustEnergy; StencilPlan: HasLossWeights; gen/codegen.cpp emit_loss_weights) ----
     // loss_weights caches w = sqrt(rho'(s)) per edge for the kernels of this linearisation: after
     // every precompute (Init, update, revert, the stand-alone entry points) and at Step start,
@@ -1027,19 +859,13 @@ private:
                             std::make_pair(&k_schur_apply_, "gen_schur_apply")})
                 OPT_HIP_CHECK(hipModuleGetFunction(kv.first, mod_, kv.second));
         }
-        if (src_.has_schur_explicit) {
-            for (auto kv : {std::make_pair(&k_schur_eblk_, "gen_schur_eblk"), std::make_pair(&k_schur_assemble_, "gen_schur_assemble"),
-                            std::make_pair(&k_schur_assemble_long_, "gen_schur_assemble_long"),
-                            std::make_pair(&k_schur_spmv_, "gen_schur_spmv")})
-                OPT_HIP_CHECK(hipModuleGetFunction(kv.first, mod_, kv.second));
+        if (matrix_form() != MatrixForm::None) {   // gen_schur_eblk ... or gen_normal_eblk ...
+            const std::string prefix = src_.has_normal ? "gen_normal_" : "gen_schur_";
+            for (auto kv : {std::make_pair(&k_mx_eblk_, "eblk"), std::make_pair(&k_mx_assemble_, "assemble"),
+                            std::make_pair(&k_mx_assemble_long_, "assemble_long"), std::make_pair(&k_mx_spmv_, "spmv")})
+                OPT_HIP_CHECK(hipModuleGetFunction(kv.first, mod_, (prefix + kv.second).c_str()));
         }
         if (src_.has_loss) OPT_HIP_CHECK(hipModuleGetFunction(&k_loss_weights_, mod_, "gen_loss_weights"));
-        if (src_.has_normal) {
-            for (auto kv : {std::make_pair(&k_normal_eblk_, "gen_normal_eblk"), std::make_pair(&k_normal_assemble_, "gen_normal_assemble"),
-                            std::make_pair(&k_normal_assemble_long_, "gen_normal_assemble_long"),
-                            std::make_pair(&k_normal_spmv_, "gen_normal_spmv")})
-                OPT_HIP_CHECK(hipModuleGetFunction(kv.first, mod_, kv.second));
-        }
         // (the strip J^T F has no block accumulation: block energies keep the gather)
         if (src_.has_jtf_strip && !slab && !m_.block_preconditioner) {
             const char* wj = getenv("OPT_AMD_GEN_JTF");
@@ -1074,55 +900,6 @@ private:
         std::vector<void*> a;
         for (const void* p : args) a.push_back(const_cast<void*>(p));
         OPT_HIP_CHECK(hipModuleLaunchKernel(f, grid, 1, 1, kBlock, 1, 1, 0, s, a.data(), nullptr));
-    }
-    // The symbolic phase on the device (schur_pattern_dev.hip) into the sx_ buffers; false, with
-    // nothing allocated, where its temporaries do not fit: that wiring takes the host path.
-    bool symbolic_device(long long nE, long long nR, const std::vector<SchurListDev>& lists, bool distinct, const char* what,
-                         int long_row, long long reserve_bytes, hipStream_t s) {
-        SchurPatternDev D;
-        const char* cap = getenv("OPT_AMD_SYMBOLIC_MAX_BYTES");
-        bool built = false;
-        try {
-            built = schur_pattern_build_dev(nE, nR, lists, distinct, what, gen::kSchurLongPairs, long_row, reserve_bytes,
-                                            cap && *cap ? atoll(cap) : -1, s, &D);
-        } catch (const std::length_error& e) {
-            throw PlanError(std::string("generic: ") + e.what());
-        }
-        sym_fallback_ = !built;
-        sym_transient_ = D.transient_bytes;
-        if (!built) return false;
-        for (size_t l = 0; l < lists.size(); ++l) sx_qb_.b[l] = D.base[l];
-        sx_nnzb_ = D.n_blocks;
-        sx_npairs_ = D.n_pairs;
-        sx_nq_ = D.n_instances;
-        sx_rowptr_ = D.rowPtr;
-        sx_colind_ = D.colInd;
-        sx_blkrow_ = D.blkRow;
-        sx_pairptr_ = D.pairPtr;
-        sx_pairs_ = D.pairs;
-        sx_nlong_ = D.n_long;
-        sx_long_ = D.longBlk;
-        if (long_row > 0) {
-            nx_nlongrow_ = D.n_longrow;
-            nx_longrow_ = D.longRow;
-        } else {
-            dfree(D.longRow);
-        }
-        sym_info_ = std::string("path=device reason=") + (symbolic_mode_ == kSymbolicDevice ? "env" : "default") + symbolic_counts();
-        return true;
-    }
-    void symbolic_host_info() {
-        const bool mem = symbolic_mode_ != kSymbolicHost && sym_fallback_;
-        if (!mem) sym_transient_ = 0;
-        sym_info_ = std::string("path=host reason=") + (mem ? "memory" : "env") + symbolic_counts();
-    }
-    std::string symbolic_counts() const {
-        return " pairs=" + std::to_string(sx_npairs_) + " blocks=" + std::to_string(sx_nnzb_) + " instances=" +
-               std::to_string(sx_nq_) + " transient_bytes=" + std::to_string(sym_transient_);
-    }
-    void schur_explicit_release() {
-        for (int** q : {&sx_rowptr_, &sx_colind_, &sx_blkrow_, &sx_pairptr_, &sx_pairs_, &sx_long_, &nx_longrow_}) { dfree(*q); *q = nullptr; }
-        for (T** q : {&sx_val_, &sx_w_, &sx_y_}) { dfree(*q); *q = nullptr; }
     }
     // vertex indices must lie in [0, N) (fail-stop, as the reference does on bad input)
     void check_graphs(hipStream_t s) {
@@ -1260,37 +1037,14 @@ private:
     T* blk_ = nullptr;                       // the plan's block buffer (set_block_buffer)
     hipFunction_t k_schur_rhs_{}, k_schur_elim_{}, k_schur_apply_{};
     T *w_ = nullptr, *be_ = nullptr;         // the plan's compact Schur vectors (set_schur_buffers)
-    // explicit S: kernels, the pattern (block-CSR, block rows, pair lists), values, W_q / Y_q
-    hipFunction_t k_schur_eblk_{}, k_schur_assemble_{}, k_schur_assemble_long_{}, k_schur_spmv_{};
-    int* sx_long_ = nullptr;                 // blocks with more than gen::kSchurLongPairs pairs
-    int sx_nlong_ = 0;
-    struct QBase { long long b[16]; } sx_qb_{};
-    unsigned long long sx_generation_ = 0;   // topology_generation_ the pattern was built for
-    long long sx_nnzb_ = 0, sx_npairs_ = 0, sx_nq_ = 0;
-    int *sx_rowptr_ = nullptr, *sx_colind_ = nullptr, *sx_blkrow_ = nullptr, *sx_pairptr_ = nullptr, *sx_pairs_ = nullptr;
-    T *sx_val_ = nullptr, *sx_w_ = nullptr, *sx_y_ = nullptr;
-    // explicit J^T J: its kernels (pattern, values and G_q live in the sx_ buffers above) and the
-    // rows with more than gen::kNormalLongRow blocks
-    hipFunction_t k_normal_eblk_{}, k_normal_assemble_{}, k_normal_assemble_long_{}, k_normal_spmv_{};
-    int* nx_longrow_ = nullptr;
-    int nx_nlongrow_ = 0;
-    // where the symbolic phase of either form runs: OPT_AMD_SYMBOLIC=host|device, read when the
-    // plan is made (unset: the device); what the last one did, for symbolic_info()
-    enum { kSymbolicDefault, kSymbolicHost, kSymbolicDevice };
-    static int symbolic_mode_from_env() {
-        const char* v = getenv("OPT_AMD_SYMBOLIC");
-        const std::string w = v ? v : "";
-        return w == "host" ? kSymbolicHost : w == "device" ? kSymbolicDevice : kSymbolicDefault;
-    }
-    const int symbolic_mode_ = symbolic_mode_from_env();
-    bool sym_fallback_ = false;
-    long long sym_transient_ = 0;
-    std::string sym_info_;
+    // the assembled S or H (matrix_form()): its eblk / assemble / SpMV kernels and its buffers
+    hipFunction_t k_mx_eblk_{}, k_mx_assemble_{}, k_mx_assemble_long_{}, k_mx_spmv_{};
+    ExplicitMatrix<T> xm_;
 };
 
 static_assert(HasBlockPre<GenericOp<float>>::value);   // the optional driver features this Op claims (stencil_plan.h)
 static_assert(HasSchur<GenericOp<float>>::value);
-static_assert(HasNormal<GenericOp<float>>::value);
+static_assert(HasExplicitMatrix<GenericOp<float>>::value);
 static_assert(HasLossWeights<GenericOp<float>>::value);
 static_assert(HasCaptureKey<GenericOp<float>>::value);
 static_assert(HasRefreshCaches<GenericOp<float>>::value);

@@ -542,6 +542,25 @@ int OptAMD_GenericPlanCheck(const char* filename, char* buf, int n) {
     copy_name(why, buf, n);
     return r;
 }
+// the pattern entry points' common end: the host or the device builder, then the counts and arrays
+// the caller asked for; -1 and the builder's message in buf where it refuses
+static int pattern_out(bool device, long long nE, long long nR, const std::vector<optamd::SchurList>& lists, bool distinct,
+                       const char* what, long long* counts, int* rowPtr, int* colInd, int* pairPtr, int* pairs, char* buf,
+                       int n) {
+    optamd::SchurPattern P;
+    try {
+        if (device) optamd::schur_pattern_build_dev_host(nE, nR, lists, distinct, what, &P);
+        else optamd::schur_pattern_build(nE, nR, lists, &P, distinct, what);
+    } catch (const std::exception& e) {
+        return copy_name(e.what(), buf, n), -1;
+    }
+    if (counts) { counts[0] = P.n_instances; counts[1] = P.n_pairs(); counts[2] = P.n_blocks(); }
+    if (rowPtr) std::copy(P.rowPtr.begin(), P.rowPtr.end(), rowPtr);
+    if (colInd) std::copy(P.colInd.begin(), P.colInd.end(), colInd);
+    if (pairPtr) std::copy(P.pairPtr.begin(), P.pairPtr.end(), pairPtr);
+    if (pairs) std::copy(P.pairs.begin(), P.pairs.end(), pairs);
+    return 0;
+}
 // OptAMD_SchurPattern / OptAMD_SchurPatternDevice: the same checks and outputs, the builder differs
 static int schur_pattern_api(bool device, long long nEliminated, long long nRetained, int nLists,
                              const int* const* elimVertex, const int* const* retVertex, const long long* nEdges,
@@ -555,19 +574,8 @@ static int schur_pattern_api(bool device, long long nEliminated, long long nReta
                 return copy_name("list " + std::to_string(l) + ": vertex index outside its space at edge " + std::to_string(e), buf, n), -1;
         lists.push_back({elimVertex[l], retVertex[l], nEdges[l]});
     }
-    optamd::SchurPattern P;
-    try {
-        if (device) optamd::schur_pattern_build_dev_host(nEliminated, nRetained, lists, false, "explicit Schur complement", &P);
-        else optamd::schur_pattern_build(nEliminated, nRetained, lists, &P);
-    } catch (const std::exception& e) {
-        return copy_name(e.what(), buf, n), -1;
-    }
-    if (counts) { counts[0] = P.n_instances; counts[1] = P.n_pairs(); counts[2] = P.n_blocks(); }
-    if (rowPtr) std::copy(P.rowPtr.begin(), P.rowPtr.end(), rowPtr);
-    if (colInd) std::copy(P.colInd.begin(), P.colInd.end(), colInd);
-    if (pairPtr) std::copy(P.pairPtr.begin(), P.pairPtr.end(), pairPtr);
-    if (pairs) std::copy(P.pairs.begin(), P.pairs.end(), pairs);
-    return 0;
+    return pattern_out(device, nEliminated, nRetained, lists, false, "explicit Schur complement", counts, rowPtr, colInd,
+                       pairPtr, pairs, buf, n);
 }
 int OptAMD_SchurPattern(long long nEliminated, long long nRetained, int nLists, const int* const* elimVertex,
                         const int* const* retVertex, const long long* nEdges, long long* counts, int* rowPtr,
@@ -606,19 +614,8 @@ static int normal_pattern_api(bool device, long long nVertices, int nLists, cons
         }
         lists.push_back({ids[l].data(), vertex[l], ne});
     }
-    optamd::SchurPattern P;
-    try {
-        if (device) optamd::schur_pattern_build_dev_host(ebase[nGraphs], nVertices, lists, true, "NormalMatrix(\"explicit\")", &P);
-        else optamd::schur_pattern_build(ebase[nGraphs], nVertices, lists, &P, true, "NormalMatrix(\"explicit\")");
-    } catch (const std::exception& e) {
-        return copy_name(e.what(), buf, n), -1;
-    }
-    if (counts) { counts[0] = P.n_instances; counts[1] = P.n_pairs(); counts[2] = P.n_blocks(); }
-    if (rowPtr) std::copy(P.rowPtr.begin(), P.rowPtr.end(), rowPtr);
-    if (colInd) std::copy(P.colInd.begin(), P.colInd.end(), colInd);
-    if (pairPtr) std::copy(P.pairPtr.begin(), P.pairPtr.end(), pairPtr);
-    if (pairs) std::copy(P.pairs.begin(), P.pairs.end(), pairs);
-    return 0;
+    return pattern_out(device, ebase[nGraphs], nVertices, lists, true, "NormalMatrix(\"explicit\")", counts, rowPtr, colInd,
+                       pairPtr, pairs, buf, n);
 }
 int OptAMD_NormalPattern(long long nVertices, int nLists, const int* const* vertex, const int* listGraph,
                          const long long* graphEdges, int nGraphs, long long* counts, int* rowPtr, int* colInd,

@@ -100,13 +100,10 @@ __global__ __launch_bounds__(kBlock) void revert_images_kernel(VecLayout L, cons
 //   HasBlockPre            block_pre(); block_entries(), set_block_buffer, block_layout,
 //                          block_init, block_step2, block_half2, block_apply
 //   HasSchur               schur(); schur_entries(), set_schur_buffers, eliminated, schur_rhs,
-//                          schur_elim, schur_apply, schur_back, and for ReducedSystem("explicit")
-//                          schur_explicit(), schur_symbolic_stale, schur_symbolic, schur_eblk,
-//                          schur_assemble, schur_spmv, schur_matrix_shape, schur_matrix_copy,
-//                          schur_explicit_key, symbolic_info
-//   HasNormal              normal(); normal_symbolic_stale, normal_symbolic, normal_eblk,
-//                          normal_assemble, normal_spmv, normal_matrix_shape, normal_matrix_copy,
-//                          normal_key
+//                          schur_elim, schur_apply, schur_back
+//   HasExplicitMatrix      matrix_form(); matrix_symbolic_stale, matrix_symbolic, matrix_eblk,
+//                          matrix_assemble, matrix_spmv, matrix_shape, matrix_copy, matrix_key,
+//                          symbolic_info
 // A trait looks for its first method by NAME only (none of these is overloaded or a
 // template): an Op whose signature drifts fails to compile where the driver calls it,
 // instead of losing the feature without a word. Each Op's source asserts the traits it
@@ -200,13 +197,17 @@ OPTAMD_OP_TRAIT(HasBlockPre, block_pre);
 // delta_e = M^-1 (b_e - E^T delta_r), and the update, model cost and cost see the full delta.
 OPTAMD_OP_TRAIT(HasSchur, schur);
 
-// Ops that can form H = J^T J explicitly (GenericOp for NormalMatrix("explicit")): normal() says
-// whether this energy asked for it (then block_pre() holds too, and schur() does not). Once per
-// Step, after jtf has left the diagonal blocks in the block buffer and before block_init inverts
-// them, normal_symbolic (only after a re-wiring), normal_eblk and normal_assemble build H
-// in block-CSR; every apply of the PCG loop — and the residual reset's, and apply_jtj's — is then
-// normal_spmv, with apply's contract. LM's diagonal is not part of H: the SpMV adds dadd p.
-OPTAMD_OP_TRAIT(HasNormal, normal);
+// Ops that can assemble the matrix PCG runs on in block-CSR (GenericOp): matrix_form() says
+// which one this energy asked for — S of ReducedSystem("explicit") (then schur() holds) or
+// H = J^T J of NormalMatrix("explicit") (then block_pre() holds and schur() does not). Once per
+// Step, before block_init inverts the blocks the assembly reads — S after schur_rhs has left
+// M_e^-1 in the block buffer, H after jtf has left the diagonal blocks there — matrix_symbolic
+// (only after a re-wiring), matrix_eblk and matrix_assemble build it; every apply of the PCG
+// loop — and the residual reset's, and apply_reduced's / apply_jtj's — is then matrix_spmv, with
+// schur_apply's / apply's contract. LM's diagonal is not part of the matrix: the SpMV adds dadd p.
+// The timer entries keep the form's name: schur_* / normal_* + symbolic, eblk, assemble, spmv.
+enum class MatrixForm { None, Schur, Normal };
+OPTAMD_OP_TRAIT(HasExplicitMatrix, matrix_form);
 
 // Ops that choose among several forms of their kernels (GenericOp: gather, LDS tiles, register
 // strips): std::string generated_forms() const, the forms this plan launches.
@@ -337,7 +338,7 @@ public:
         linear_init(rz(0), true);   // PCGInit1 (+ LM diagonal)
         if (lm_) OPT_HIP_CHECK(hipMemsetAsync(red_.scalars + kScQ0, 0, sizeof(double), stream_));
         schur_prepare(true);   // (delta_ = 0 here: the p of the reduced right-hand side's apply)
-        normal_prepare();
+        if (matrix_ == MatrixForm::Normal) explicit_prepare();   // H from jtf's diagonal blocks (S: in schur_prepare)
         if constexpr (HasBlockPre<Op>::value)
             if (block_) {   // M_e^-1 in place of the blocks, z_0 = M^-1 r, p_0 = z_0, rz_0
                 tbegin("blk_init");
@@ -460,10 +461,8 @@ public:
             key.push_back((unsigned long long)(uintptr_t)z_);
         }
         if (schur_) key.push_back((unsigned long long)(uintptr_t)w_);
-        if constexpr (HasSchur<Op>::value)
-            if (explicit_) op_->schur_explicit_key(&key);
-        if constexpr (HasNormal<Op>::value)
-            if (normal_) op_->normal_key(&key);
+        if constexpr (HasExplicitMatrix<Op>::value)
+            if (matrix_ != MatrixForm::None) op_->matrix_key(&key);
         if constexpr (!HasCaptureKey<Op>::value) {
             for (const DeclImage& im : spec_.images)   // arrays by address, scalars by value (below)
                 if (im.index >= 0 && im.index < spec_.n_params_total)
@@ -619,61 +618,27 @@ public:
         return Plan::apply_reduced(params, pin, Sp);
     }
     bool reduced_matrix_shape(long long* rows, int* dim, long long* nnzb) const override {
-        if constexpr (HasSchur<Op>::value)
-            if (explicit_) return op_->schur_matrix_shape(rows, dim, nnzb);
-        return Plan::reduced_matrix_shape(rows, dim, nnzb);
+        return explicit_shape(MatrixForm::Schur, rows, dim, nnzb);
     }
     // S at the current unknowns: the preparation of apply_reduced (whose schur_prepare runs
     // the numeric phase), then the block-CSR copied out; every buffer the preparation writes
     // is rebuilt by the next step
     int reduced_matrix(void** params, int* rowPtr, int* colInd, void* val) override {
-        if constexpr (HasSchur<Op>::value) {
-            if (!explicit_) return 1;
-            begin_call();
-            if (!rowPtr) {   // bind + pattern only
-                op_->bind(params, stream_);
-                schur_symbolic();
-            } else {
-                reduced_prepare(params);
-                op_->schur_matrix_copy(rowPtr, colInd, (T*)val, stream_);
-            }
-            end_call();
-            return 0;
-        }
-        return Plan::reduced_matrix(params, rowPtr, colInd, val);
+        return explicit_matrix(MatrixForm::Schur, params, rowPtr, colInd, val);
     }
     // what the last symbolic phase of S or H did; -1 on a plan with neither statement
     int symbolic_info(std::string* line) const override {
-        if constexpr (HasSchur<Op>::value)
-            if (explicit_) return *line = op_->symbolic_info(), 0;
-        if constexpr (HasNormal<Op>::value)
-            if (normal_) return *line = op_->symbolic_info(), 0;
+        if constexpr (HasExplicitMatrix<Op>::value)
+            if (matrix_ != MatrixForm::None) return *line = op_->symbolic_info(), 0;
         return Plan::symbolic_info(line);
     }
     bool normal_matrix_shape(long long* rows, int* dim, long long* nnzb) const override {
-        if constexpr (HasNormal<Op>::value)
-            if (normal_) return op_->normal_matrix_shape(rows, dim, nnzb);
-        return Plan::normal_matrix_shape(rows, dim, nnzb);
+        return explicit_shape(MatrixForm::Normal, rows, dim, nnzb);
     }
     // H at the current unknowns: bind, J^T F with its diagonal blocks, the numeric phase, then
     // the block-CSR copied out; every buffer this writes is rebuilt by the next step
     int normal_matrix(void** params, int* rowPtr, int* colInd, void* val) override {
-        if constexpr (HasNormal<Op>::value) {
-            if (!normal_) return 1;
-            begin_call();
-            if (!rowPtr) {   // bind + pattern only
-                op_->bind(params, stream_);
-                normal_symbolic();
-            } else {
-                prepare(params);
-                op_->jtf(r_, diag_, flags_, stream_);
-                normal_prepare();
-                op_->normal_matrix_copy(rowPtr, colInd, (T*)val, stream_);
-            }
-            end_call();
-            return 0;
-        }
-        return Plan::normal_matrix(params, rowPtr, colInd, val);
+        return explicit_matrix(MatrixForm::Normal, params, rowPtr, colInd, val);
     }
     int loss_groups(int max_groups, int* graph, int* residuals, int* kind) const override {
         if constexpr (HasLossWeights<Op>::value) return op_->loss_groups(max_groups, graph, residuals, kind);
@@ -710,9 +675,9 @@ public:
         if (mat_) {
             materialize();
             mat_apply((const T*)p, (T*)Ap, nullptr, kScTmp);
-        } else if (normal_) {   // the explicit path: H from this call's blocks, then the SpMV
-            normal_prepare();
-            normal_apply((const T*)p, (T*)Ap, nullptr, nullptr, red_.slot(nb(), kScTmp));
+        } else if (matrix_ == MatrixForm::Normal) {   // the explicit path: H from this call's blocks, then the SpMV
+            explicit_prepare();
+            explicit_apply((const T*)p, (T*)Ap, nullptr, nullptr, red_.slot(nb(), kScTmp));
         } else {
             tbegin(Op::kApplyName);   // the same timer entry as the PCG loop's applies
             op_->apply((const T*)p, (T*)Ap, nullptr, nullptr, red_.slot(nb(), kScTmp), stream_);
@@ -830,10 +795,9 @@ private:
                 OPT_HIP_CHECK(hipMemset(w_, 0, sizeof(T) * ne));
                 OPT_HIP_CHECK(hipMemset(be_, 0, sizeof(T) * ne));
                 op_->set_schur_buffers(w_, be_);
-                explicit_ = op_->schur_explicit();
             }
         }
-        if constexpr (HasNormal<Op>::value) normal_ = op_->normal();
+        if constexpr (HasExplicitMatrix<Op>::value) matrix_ = op_->matrix_form();
         flags_ = (uint8_t*)dmalloc(dom_.npix_mem());
         OPT_HIP_CHECK(hipMemset(flags_, 0, dom_.npix_mem()));
         red_.ensure(std::max(op_->stencil_blocks(), 4096), 2, 64);
@@ -894,43 +858,67 @@ private:
         if (timed) tend();
         OPT_HIP_CHECK(hipGetLastError());
     }
-    // explicit plans: the pattern of S for the graphs as bound (a no-op while the wiring
-    // stands). A rebuild moves the SpMV's buffers, so no captured loop survives it.
-    void schur_symbolic() {
-        if constexpr (HasSchur<Op>::value)
-            if (explicit_ && op_->schur_symbolic_stale()) {
+    // ---- the assembled matrix of an explicit plan (HasExplicitMatrix) ----
+    // the timer entry of a stage: it carries the form's name
+    const char* explicit_name(const char* schur, const char* normal) const {
+        return matrix_ == MatrixForm::Schur ? schur : normal;
+    }
+    bool explicit_shape(MatrixForm form, long long* rows, int* dim, long long* nnzb) const {
+        if constexpr (HasExplicitMatrix<Op>::value)
+            if (matrix_ == form) return op_->matrix_shape(rows, dim, nnzb);
+        (void)form; (void)rows; (void)dim; (void)nnzb;
+        return false;
+    }
+    // the matrix at the current unknowns copied out, or (no arrays) bind + pattern only; 1 on a
+    // plan without that matrix
+    int explicit_matrix(MatrixForm form, void** params, int* rowPtr, int* colInd, void* val) {
+        if constexpr (HasExplicitMatrix<Op>::value) {
+            if (matrix_ != form) return 1;
+            begin_call();
+            if (!rowPtr) {
+                op_->bind(params, stream_);
+                explicit_symbolic();
+            } else {
+                if (form == MatrixForm::Schur) {
+                    reduced_prepare(params);
+                } else {
+                    prepare(params);
+                    op_->jtf(r_, diag_, flags_, stream_);
+                    explicit_prepare();
+                }
+                op_->matrix_copy(rowPtr, colInd, (T*)val, stream_);
+            }
+            end_call();
+            return 0;
+        }
+        (void)form; (void)params; (void)rowPtr; (void)colInd; (void)val;
+        return 1;
+    }
+    // the pattern for the graphs as bound (a no-op while the wiring stands). A rebuild moves the
+    // SpMV's buffers, so no captured loop survives it.
+    void explicit_symbolic() {
+        if constexpr (HasExplicitMatrix<Op>::value)
+            if (matrix_ != MatrixForm::None && op_->matrix_symbolic_stale()) {
                 drop_graph();
-                tbegin("schur_symbolic");
-                op_->schur_symbolic(stream_);
+                tbegin(explicit_name("schur_symbolic", "normal_symbolic"));
+                op_->matrix_symbolic(stream_);
                 tend();
             }
     }
-
-    // NormalMatrix("explicit") plans: the pattern of H for the graphs as bound (a no-op
-    // while the wiring stands). A rebuild moves the SpMV's buffers, so no captured loop survives.
-    void normal_symbolic() {
-        if constexpr (HasNormal<Op>::value)
-            if (normal_ && op_->normal_symbolic_stale()) {
-                drop_graph();
-                tbegin("normal_symbolic");
-                op_->normal_symbolic(stream_);
-                tend();
+    // ... and the matrix itself from the blocks in blk_, before block_init inverts them
+    void explicit_prepare() {
+        if constexpr (HasExplicitMatrix<Op>::value)
+            if (matrix_ != MatrixForm::None) {
+                explicit_symbolic();
+                tbegin(explicit_name("schur_eblk", "normal_eblk")); op_->matrix_eblk(stream_); tend();
+                tbegin(explicit_name("schur_assemble", "normal_assemble")); op_->matrix_assemble(stream_); tend();
             }
     }
-    // ... after jtf and before block_init: H itself from the diagonal blocks in blk_
-    void normal_prepare() {
-        if constexpr (HasNormal<Op>::value)
-            if (normal_) {
-                normal_symbolic();
-                tbegin("normal_eblk"); op_->normal_eblk(stream_); tend();
-                tbegin("normal_assemble"); op_->normal_assemble(stream_); tend();
-            }
-    }
-    // Ap = H p (+ dadd p) by the block SpMV; false on any other plan
-    bool normal_apply(const T* p, T* Ap, const T* dadd, const int* stop, ReduceSlot rs) {
-        if constexpr (HasNormal<Op>::value)
-            if (normal_) {
-                tbegin("normal_spmv"); op_->normal_spmv(p, Ap, dadd, stop, rs, stream_); tend();
+    // Ap = S p or H p (+ dadd p) by the block SpMV; false on any other plan
+    bool explicit_apply(const T* p, T* Ap, const T* dadd, const int* stop, ReduceSlot rs) {
+        if constexpr (HasExplicitMatrix<Op>::value)
+            if (matrix_ != MatrixForm::None) {
+                tbegin(explicit_name("schur_spmv", "normal_spmv")); op_->matrix_spmv(p, Ap, dadd, stop, rs, stream_); tend();
                 return true;
             }
         (void)p; (void)Ap; (void)dadd; (void)stop; (void)rs;
@@ -953,21 +941,13 @@ private:
                     OPT_HIP_CHECK(hipGetLastError());
                 }
                 tend();
-                if (explicit_) {   // S itself: M_e^-1 is in blk, B_r not yet inverted
-                    schur_symbolic();
-                    tbegin("schur_eblk"); op_->schur_eblk(stream_); tend();
-                    tbegin("schur_assemble"); op_->schur_assemble(stream_); tend();
-                }
+                if (matrix_ == MatrixForm::Schur) explicit_prepare();   // S itself: M_e^-1 is in blk, B_r not yet inverted
             }
     }
-    // the reduced apply Ap = S p (two launches, or the block SpMV of an explicit plan); false
-    // on a plan without Eliminate
+    // the reduced apply Ap = S p (two launches; an explicit plan's is explicit_apply); false on
+    // a plan without Eliminate
     bool schur_apply(const T* p, T* Ap, const T* dadd, const int* stop, ReduceSlot rs) {
-        if constexpr (HasSchur<Op>::value)
-            if (schur_ && explicit_) {
-                tbegin("schur_spmv"); op_->schur_spmv(p, Ap, dadd, stop, rs, stream_); tend();
-                return true;
-            }
+        if (matrix_ == MatrixForm::Schur) return explicit_apply(p, Ap, dadd, stop, rs);
         if constexpr (HasSchur<Op>::value)
             if (schur_) {
                 tbegin("schur_elim"); op_->schur_elim(p, stream_); tend();
@@ -1040,7 +1020,7 @@ private:
             }
         }
         if (schur_apply(p_, Ap_, dadd, stop, rs)) return;
-        if (normal_apply(p_, Ap_, dadd, stop, rs)) return;
+        if (explicit_apply(p_, Ap_, dadd, stop, rs)) return;
         tbegin(Op::kApplyName);
         op_->apply(p_, Ap_, dadd, stop, rs, stream_);
         tend();
@@ -1110,7 +1090,7 @@ private:
     void pcg_reset_apply(const int* stop) {
         exchange_vec(delta_);
         if (!schur_apply(delta_, Adelta_, CtC_, stop, red_.slot(nb(), kScTmp)) &&
-            !normal_apply(delta_, Adelta_, CtC_, stop, red_.slot(nb(), kScTmp)))
+            !explicit_apply(delta_, Adelta_, CtC_, stop, red_.slot(nb(), kScTmp)))
             op_->apply(delta_, Adelta_, CtC_, stop, red_.slot(nb(), kScTmp), stream_);
     }
     void pcg_half2(int i, const int* stop, const ZetaArgs& z) {
@@ -1296,8 +1276,7 @@ private:
     T *blk_ = nullptr, *z_ = nullptr;          // its blocks (inverted in place) and z = M^-1 r
     bool schur_ = false;                       // Eliminate: PCG on the Schur complement (HasSchur)
     T *w_ = nullptr, *be_ = nullptr;           // compact (eliminated elements): M^-1-sized products, the stash of b_e
-    bool explicit_ = false;                    // ReducedSystem("explicit"): S assembled per step, the apply a block SpMV
-    bool normal_ = false;                      // NormalMatrix("explicit"): H assembled per step, the apply a block SpMV (HasNormal)
+    MatrixForm matrix_ = MatrixForm::None;     // S or H assembled per step, the apply a block SpMV (HasExplicitMatrix)
     uint8_t* flags_ = nullptr;
     int* stop_ = nullptr;
     hipGraphExec_t graph_exec_ = nullptr;      // captured PCG loop (pcg_graph_begin)

@@ -15,6 +15,7 @@ import pytest
 
 from opt_amd import OptSolver, workloads
 from tests import test_arap_gpu as arap
+from tests import test_pose_graph_gpu as pg
 from tests import test_schur_gpu as ba
 from tests import test_sfs_gpu as sfs
 from tests.iw_helpers import ROOT
@@ -24,11 +25,12 @@ L, P = 7, 3
 R = L // P
 POISSON = os.path.join(ROOT, "energies", "poisson_image_editing.t")
 EXPLICIT = os.path.join(ROOT, "energies", "bundle_adjustment_schur_explicit.t")
+NORMAL = os.path.join(ROOT, "energies", "normal_matrix", "pose_graph_2d_explicit.t")
 GN, LM = "gaussNewtonGPU", "LMGPU"
 # every name some case counts: a case expects 0 of the ones it does not list
 NAMES = ["jtf", "gn_init", "lm_init", "step2", "step3", "step23", "blk_init", "blk_step2", "blk_half2",
          "schur_rhs", "schur_elim", "schur_apply", "schur_back", "schur_eblk", "schur_assemble", "schur_spmv",
-         "schur_symbolic", "saveJToCRS", "gen_apply"]
+         "schur_symbolic", "normal_symbolic", "normal_eblk", "normal_assemble", "normal_spmv", "saveJToCRS", "gen_apply"]
 
 
 def poisson(kind, tmp_path=None, **kw):
@@ -57,6 +59,11 @@ def bundle(path, block=False):
             energy.write_text(open(path).read().replace("UsePreconditioner(true)", 'UsePreconditioner("block")'))
         return ba.solver(w, kind, path=str(energy)), ba.bundle_params(w, False)[0]
     return make
+
+
+def poses(kind, tmp_path=None):
+    w = pg.arrays(40)
+    return pg.solver(w, kind, energy=NORMAL), pg.params(w, False)[0]
 
 
 def common(lm):
@@ -95,6 +102,15 @@ def schur_explicit(lm, first=True):
     return d
 
 
+def normal_explicit(lm, first=True):
+    """H assembled once per Step, every apply (the reset's included) one block SpMV; the pattern
+    of H once per wiring"""
+    d = block(lm)
+    del d["A"]
+    return {**d, "normal_eblk": 1, "normal_assemble": 1, "normal_spmv": L + R if lm else L,
+            "normal_symbolic": 1 if first else 0, "gen_apply": 0}
+
+
 def materialized(lm):
     """J assembled once per Step; the loop's applies are the SpMV pair (A = its second), the
     family's own apply only the reset's untimed one"""
@@ -115,6 +131,8 @@ CASES = {
     "schur-LM": (bundle(ba.SCHUR), LM, {}, schur),
     "explicit-GN": (bundle(EXPLICIT), GN, {}, schur_explicit),
     "explicit-LM": (bundle(EXPLICIT), LM, {}, schur_explicit),
+    "normal-GN": (poses, GN, {}, normal_explicit),
+    "normal-LM": (poses, LM, {}, normal_explicit),
     "materialized-LM": (lambda kind, tmp_path: poisson(kind, materialized=True), LM, {}, materialized),
 }
 
@@ -143,7 +161,7 @@ def test_launches_of_one_step(monkeypatch, tmp_path, case):
     names = NAMES + [n for n in (A, plain) if n not in NAMES]
     s.init(prm)
     steps = [step_counts(s, names)]
-    if expected is schur_explicit:
+    if expected in (schur_explicit, normal_explicit):
         steps.append(step_counts(s, names))   # the same graphs: no second symbolic phase
     for k, got in enumerate(steps):
         want = expected(kind == LM) if k == 0 else expected(kind == LM, first=False)
