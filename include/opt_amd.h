@@ -176,6 +176,26 @@ int OptAMD_SchurPatternDevice(long long nEliminated, long long nRetained, int nL
  * ReducedSystem("explicit") nor NormalMatrix("explicit"), or for NULL. */
 int OptAMD_PlanSymbolicInfo(Opt_Plan* plan, char* buf, int buflen);
 
+/* The direct solver: LinearSolver("cholesky") in an energy file beside ReducedSystem("explicit")
+ * or NormalMatrix("explicit") makes every Step with lIterations > 0 take the exact Gauss-Newton /
+ * LM step: the assembled S or H plus LM's clamped diagonal is filled into 64 x 64 tiles of a
+ * dense lower triangle (rows and columns of excluded elements as identity rows), factored
+ * A = L L^T by the blocked MFMA kernels of OptAMD_DenseCholesky and solved for the retained
+ * delta; back-substitution, update, model cost and LM's accept / revert follow as after PCG.
+ * lIterations only switches the linear solve on (> 0) or off; q_tolerance and
+ * residual_reset_period do not apply. LinearSolver("pcg"), or no statement, is the PCG loop.
+ * A Step falls back to the explicit plan's PCG loop, bitwise what the file without the statement
+ * does, when the dense storage exceeds OPT_AMD_DENSE_MAX_BYTES (default 2 GiB) or the free
+ * device memory (reason=memory), or when a pivot fails: NaN, not positive, or <= eps * the row's
+ * original diagonal entry (reason=pivot; the host reads the flag once per Step after the
+ * factorisation). One line of key=value words in buf:
+ *   n=N tiles=N bytes=N factorisations=N fallbacks=N reason=none|memory|pivot min_pivot_ratio=X
+ * n the padded-free dimension, tiles the stored 64 x 64 tiles, bytes the dense storage,
+ * factorisations / fallbacks the Steps that took either path, reason the last fall-back's,
+ * min_pivot_ratio the smallest pivot / original diagonal of the last completed factorisation (inf before
+ * the first). Returns the line's length, -1 on a plan without the statement, or for NULL. */
+int OptAMD_PlanDirectInfo(Opt_Plan* plan, char* buf, int buflen);
+
 /* The explicitly formed normal matrix: NormalMatrix("explicit") in an energy file whose unknowns
  * lie over one index space makes the plan assemble H = J^T J once per Step in block-CSR (blocks
  * of blockDim x blockDim, blockDim the channels of all unknowns of one element, row-major inside
@@ -213,6 +233,19 @@ int OptAMD_NormalPattern(long long nVertices, int nLists, const int* const* vert
 int OptAMD_NormalPatternDevice(long long nVertices, int nLists, const int* const* vertex, const int* listGraph,
                                const long long* graphEdges, int nGraphs, long long* counts, int* rowPtr, int* colInd,
                                int* pairPtr, int* pairs, char* buf, int buflen);
+
+/* A dense Cholesky factorisation and solve on the current device, with no plan and no energy
+ * file: A (n x n, row-major, symmetric positive definite; both triangles are read) and b are
+ * host arrays of float, or of double with isDouble != 0. The matrix is packed into 64 x 64 tiles
+ * of the lower triangle (n padded to a multiple of 64 with an identity), factored A = L L^T by
+ * the blocked right-looking MFMA kernels and solved by the two triangular launch chains; L_out
+ * (n x n, row-major, lower triangle, zeros above) and x_out (n) receive the factor and the
+ * solution of A x = b. *info is -1, or the first row whose pivot failed: NaN, not positive, or
+ * <= eps * a_ii of the precision; then every later kernel of the chain returns at entry and
+ * L_out and x_out are left untouched. Two calls on the same inputs agree bitwise. Returns 0,
+ * or -1 for invalid arguments or a matrix whose storage does not fit the device. */
+int OptAMD_DenseCholesky(long long n, const void* A, const void* b, void* L_out, void* x_out, int isDouble,
+                         long long* info);
 
 /* Ap = J^T J p at the current unknowns (+ CtC*p for LM plans, with the CtC of the
  * last LM step) and *p_dot_Ap = p.Ap (reference kernels.PCGStep1,

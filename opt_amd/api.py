@@ -116,6 +116,7 @@ _SIGNATURES = [
                                                  ctypes.POINTER(ctypes.c_longlong), _VP, _VP, _VP, _VP, ctypes.c_char_p,
                                                  ctypes.c_int]),
     ("OptAMD_PlanSymbolicInfo", ctypes.c_int, [_VP, ctypes.c_char_p, ctypes.c_int]),
+    ("OptAMD_PlanDirectInfo", ctypes.c_int, [_VP, ctypes.c_char_p, ctypes.c_int]),
     ("OptAMD_PlanNormalMatrixShape", ctypes.c_int, [_VP, ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_int),
                                                     ctypes.POINTER(ctypes.c_longlong)]),
     ("OptAMD_NormalMatrix", ctypes.c_int, [_VP, ctypes.POINTER(_VP), _VP, _VP, _VP]),
@@ -127,6 +128,8 @@ _SIGNATURES = [
                                                   ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_longlong), ctypes.c_int,
                                                   ctypes.POINTER(ctypes.c_longlong), _VP, _VP, _VP, _VP, ctypes.c_char_p,
                                                   ctypes.c_int]),
+    ("OptAMD_DenseCholesky", ctypes.c_int, [ctypes.c_longlong, _VP, _VP, _VP, _VP, ctypes.c_int,
+                                            ctypes.POINTER(ctypes.c_longlong)]),
     ("OptAMD_GenericCompileCheck", ctypes.c_int, [ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]),
     ("OptAMD_GenericForms", ctypes.c_int, [ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]),
 ]
@@ -426,6 +429,17 @@ class OptSolver:
             return -1
         return buf.value.decode()
 
+    def direct_info(self):
+        """What LinearSolver("cholesky") did on this plan so far (OptAMD_PlanDirectInfo): a dict
+        with n, tiles, bytes, factorisations, fallbacks (ints), reason ('none', 'memory' or
+        'pivot': the last fall-back's) and min_pivot_ratio (float, of the last factorisation);
+        None on a plan without the statement."""
+        buf = ctypes.create_string_buffer(256)
+        if self.lib.OptAMD_PlanDirectInfo(self.plan, buf, 256) < 0:
+            return None
+        kv = dict(w.split("=", 1) for w in buf.value.decode().split())
+        return {k: (v if k == "reason" else float(v) if k == "min_pivot_ratio" else int(v)) for k, v in kv.items()}
+
     def normal_matrix_shape(self):
         """(block rows, block dimension, blocks) of the explicitly formed H = J^T J once the
         graphs are bound (OptAMD_PlanNormalMatrixShape); None on any other plan, or before."""
@@ -695,6 +709,31 @@ def normal_pattern(n_vertices: int, lists, graph_edges=None, device: bool = Fals
           pair_ptr.ctypes.data, pairs.ctypes.data, buf, 512):
         raise OptError(buf.value.decode())
     return {"instances": nq, "pairs": npairs, "blocks": nnzb}, row_ptr, col_ind, pair_ptr, pairs
+
+
+def dense_cholesky(A, b, L=None, x=None):
+    """Dense Cholesky factorisation and solve on the device (OptAMD_DenseCholesky): A (n x n,
+    symmetric positive definite) and b (n) as float32 or float64 numpy arrays (A's dtype decides).
+    Returns (L, x, info): the lower-triangular factor, the solution of A x = b and -1; where the
+    pivot of a row fails, info is that row and L and x (the caller's contiguous arrays of A's
+    dtype where given, else zeros) are left untouched."""
+    import numpy as np
+    dt = np.float64 if np.asarray(A).dtype == np.float64 else np.float32
+    A = np.ascontiguousarray(A, dt)
+    b = np.ascontiguousarray(b, dt)
+    n = A.shape[0]
+    if A.shape != (n, n) or b.shape != (n,) or n < 1:
+        raise OptError("dense_cholesky: A must be n x n and b of length n, n >= 1")
+    L = np.zeros((n, n), dt) if L is None else L
+    x = np.zeros(n, dt) if x is None else x
+    for o, shape in ((L, (n, n)), (x, (n,))):
+        if o.dtype != dt or o.shape != shape or not o.flags.c_contiguous:
+            raise OptError("dense_cholesky: L and x must be contiguous arrays of A's dtype and shape")
+    info = ctypes.c_longlong(-1)
+    if load_library().OptAMD_DenseCholesky(n, A.ctypes.data, b.ctypes.data, L.ctypes.data, x.ctypes.data,
+                                           int(dt == np.float64), ctypes.byref(info)):
+        raise OptError("OptAMD_DenseCholesky: invalid arguments, or the matrix does not fit the device")
+    return L, x, int(info.value)
 
 
 def problem_family(energy_file: str, solver_kind: str = "gaussNewtonGPU") -> str:

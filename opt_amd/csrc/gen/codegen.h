@@ -101,6 +101,9 @@ struct GenSource {
     int normal_c = 0, normal_r = 0, normal_space = -1;
     struct NormalList { int graph; int slot; };
     std::vector<NormalList> normal_lists;
+    // LinearSolver("cholesky") beside one of the two explicit forms (codegen_dense.cpp):
+    // gen_dense_fill and gen_dense_store emitted
+    bool has_dense = false;
     // RobustEnergy (GModel::loss): gen_loss_weights emitted. loss_inc[i] = (group, GenArgs::slot
     // index): GenArgs::lwq[i] holds that group's weights in that slot's incidence order — one
     // entry per slot through which the group's residuals read an unknown

@@ -250,6 +250,7 @@ void emit_schur_explicit(Ctx& cx, std::ostringstream& o);            // gen_schu
 void emit_pair_assemble(std::ostringstream& o, const std::string& name, int CR, int CE, const std::string& Gr, bool minus,
                         bool packed = false);
 void emit_group_rows(const Ctx& cx, std::ostringstream& o, const GBlockGroup& GR);
+void emit_dense(Ctx& cx, std::ostringstream& o, const std::string& Gr, int C);   // gen_dense_fill, gen_dense_store (LinearSolver("cholesky"))
 void emit_normal(Ctx& cx, std::ostringstream& o);                    // gen_normal_eblk, gen_normal_assemble, gen_normal_spmv
 
 }  // namespace gen

@@ -190,6 +190,7 @@ void emit_normal(Ctx& cx, std::ostringstream& o) {
          "        }\n"
          "    }\n"
          "    double v[1] = {(double)dot};\n    block_reduce_publish<1>(v, rs, blockIdx.x);\n}\n";
+    emit_dense(cx, o, Gr, C);
 }
 
 }  // namespace gen

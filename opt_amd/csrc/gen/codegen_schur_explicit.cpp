@@ -343,6 +343,7 @@ void emit_schur_explicit(Ctx& cx, std::ostringstream& o) {
          "        for (int c = 0; c < C; ++c) Ap[x[c]] = (T)0;\n"
          "    }\n    }\n"
          "    double v[1] = {(double)dot};\n    block_reduce_publish<1>(v, rs, blockIdx.x);\n}\n";
+    emit_dense(cx, o, Gr, CR);
 }
 
 }  // namespace gen

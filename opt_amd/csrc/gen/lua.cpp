@@ -990,6 +990,7 @@ private:
     int n_eliminate_ = 0;   // Eliminate statements seen
     int n_reduced_ = 0;     // ReducedSystem statements seen
     int n_normal_ = 0;      // NormalMatrix statements seen
+    int n_linear_ = 0;      // LinearSolver statements seen
     void note_index(int idx) { m_->n_params_total = std::max(m_->n_params_total, idx + 1); }
     int channels_of(const Value& t) {
         if (t.k == V::Type) return t.id;
@@ -1296,6 +1297,13 @@ void Interp::install() {
         if (a.size() != 1 || a[0].k != V::Str || (a[0].s != "explicit" && a[0].s != "matrix_free"))
             err("NormalMatrix(form): form is \"explicit\" or \"matrix_free\"");
         m_->normal_explicit = a[0].s == "explicit";
+        return VList{};
+    });
+    def("LinearSolver", [this](VList& a) {
+        if (++n_linear_ > 1) err("a second LinearSolver (a Step has one linear solver)");
+        if (a.size() != 1 || a[0].k != V::Str || (a[0].s != "cholesky" && a[0].s != "pcg"))
+            err("LinearSolver(kind): kind is \"cholesky\" or \"pcg\"");
+        m_->direct_cholesky = a[0].s == "cholesky";
         return VList{};
     });
     def("Exclude", [this](VList& a) {
@@ -1763,6 +1771,9 @@ void Interp::check_eliminate() {
         throw LuaError("NormalMatrix: the energy has an Eliminate statement (its explicitly formed system is "
                        "ReducedSystem(\"explicit\"))");
     if (m_->normal_explicit) m_->use_preconditioner = m_->block_preconditioner = true;   // as UsePreconditioner("block")
+    if (m_->direct_cholesky && !m_->reduced_explicit && !m_->normal_explicit)
+        throw LuaError("LinearSolver(\"cholesky\"): the file has neither ReducedSystem(\"explicit\") nor "
+                       "NormalMatrix(\"explicit\") (the factorisation needs the assembled matrix of one of them)");
     if (m_->eliminated.empty()) return;
     const std::vector<int> unk = m_->unknown_images();
     const int sp = m_->images[m_->eliminated[0]].space;

@@ -114,6 +114,10 @@ struct GModel {
     // is a block SpMV (codegen_normal.cpp); "matrix_free" / no statement: the gather apply. Turns
     // the block preconditioner on. The shapes this form takes: normal_refusal()
     bool normal_explicit = false;
+    // LinearSolver("cholesky") beside one of the two explicit statements: the Step's linear system
+    // is the assembled matrix, filled into dense tiles, factored and solved (dense_cholesky.h,
+    // codegen_dense.cpp) instead of iterated on; "pcg" / no statement: the PCG loop
+    bool direct_cholesky = false;
     std::vector<GLossGroup> loss;  // RobustEnergy statements, in order (at most kMaxLossGroups)
     static constexpr int kMaxLossGroups = 4;
     int loss_group_of(int residual) const {   // the group a residual template belongs to, -1 = plain

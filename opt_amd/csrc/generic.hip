@@ -219,6 +219,8 @@ bool generic_signature(const std::string& text, std::string* sig, bool* use_pre,
     if (m.schur()) s += "S" + std::to_string(m.elim_space) + ";";
     // ReducedSystem("explicit"): the reduced system's form ("implicit" is no statement)
     if (m.schur() && m.reduced_explicit) s += "RX;";
+    // LinearSolver("cholesky"): the Step's linear solver ("pcg" is no statement)
+    if (m.direct_cholesky) s += "DC;";
     // RobustEnergy: per loss group its graph, kind and residual count (the scale is in the
     // templates' W leaf only by group, so kind and count are named here)
     for (auto& L : m.loss)
@@ -658,6 +660,19 @@ public:
     void matrix_copy(int* rowPtr, int* colInd, T* val, hipStream_t s) { xm_.copy_out(rowPtr, colInd, val, s); }
     void matrix_key(std::vector<unsigned long long>* key) const { xm_.capture_key(key); }
     const std::string& symbolic_info() const { return xm_.info(); }
+    // ---- LinearSolver("cholesky") (StencilPlan: direct_step; gen/codegen_dense.cpp) ----
+    // dense_fill: the assembled matrix plus dadd into the zeroed tiles of a DenseFactor, the
+    // original diagonal and the right-hand side from r; dense_store: the solution into delta.
+    bool direct_solver() const { return src_.has_dense; }
+    void dense_fill(const T* dadd, const T* r, T* tiles, T* diag0, T* rhs, hipStream_t s) {
+        const auto& m = xm_.buffers();
+        const long long nnzb = m.nnzb;
+        const int grid = (int)std::max<long long>(1, std::min<long long>(nnzb, 1 << 20));
+        launch_grid(k_dense_fill_, grid, s, {&a_, &m.blkRow, &m.colInd, &m.val, &nnzb, &dadd, &r, &tiles, &diag0, &rhs});
+    }
+    void dense_store(const T* x, T* delta, const int* fail, hipStream_t s) {
+        launch(k_dense_store_, s, {&a_, &x, &delta, &fail});
+    }
     // ---- robust losses (RobustEnergy; StencilPlan: HasLossWeights; gen/codegen.cpp emit_loss_weights) ----
     // loss_weights caches w = sqrt(rho'(s)) per edge for the kernels of this linearisation: after
     // every precompute (Init, update, revert, the stand-alone entry points) and at Step start,
@@ -865,6 +880,10 @@ private:
                             std::make_pair(&k_mx_assemble_long_, "assemble_long"), std::make_pair(&k_mx_spmv_, "spmv")})
                 OPT_HIP_CHECK(hipModuleGetFunction(kv.first, mod_, (prefix + kv.second).c_str()));
         }
+        if (src_.has_dense) {
+            OPT_HIP_CHECK(hipModuleGetFunction(&k_dense_fill_, mod_, "gen_dense_fill"));
+            OPT_HIP_CHECK(hipModuleGetFunction(&k_dense_store_, mod_, "gen_dense_store"));
+        }
         if (src_.has_loss) OPT_HIP_CHECK(hipModuleGetFunction(&k_loss_weights_, mod_, "gen_loss_weights"));
         // (the strip J^T F has no block accumulation: block energies keep the gather)
         if (src_.has_jtf_strip && !slab && !m_.block_preconditioner) {
@@ -1039,6 +1058,7 @@ private:
     T *w_ = nullptr, *be_ = nullptr;         // the plan's compact Schur vectors (set_schur_buffers)
     // the assembled S or H (matrix_form()): its eblk / assemble / SpMV kernels and its buffers
     hipFunction_t k_mx_eblk_{}, k_mx_assemble_{}, k_mx_assemble_long_{}, k_mx_spmv_{};
+    hipFunction_t k_dense_fill_{}, k_dense_store_{};
     ExplicitMatrix<T> xm_;
 };
 

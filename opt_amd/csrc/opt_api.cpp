@@ -13,6 +13,7 @@
 #include "../../include/Opt.h"
 #include "../../include/opt_amd.h"
 #include "csr.h"
+#include "dense_cholesky.h"
 #include "plan.h"
 #include "problem.h"
 #include "schur_pattern.h"
@@ -279,6 +280,12 @@ int OptAMD_PlanSymbolicInfo(Opt_Plan* plan, char* buf, int n) {
     if (!valid_plan(plan, "OptAMD_PlanSymbolicInfo")) return -1;
     std::string line;
     if (plan->impl->symbolic_info(&line) < 0) return -1;
+    return copy_name(line, buf, n);
+}
+int OptAMD_PlanDirectInfo(Opt_Plan* plan, char* buf, int n) {
+    if (!valid_plan(plan, "OptAMD_PlanDirectInfo")) return -1;
+    std::string line;
+    if (plan->impl->direct_info(&line) < 0) return -1;
     return copy_name(line, buf, n);
 }
 int OptAMD_ReducedMatrix(Opt_Plan* plan, void** params, int* rowPtr, int* colInd, void* val) {
@@ -628,6 +635,15 @@ int OptAMD_NormalPatternDevice(long long nVertices, int nLists, const int* const
                                int* pairPtr, int* pairs, char* buf, int n) {
     return normal_pattern_api(true, nVertices, nLists, vertex, listGraph, graphEdges, nGraphs, counts, rowPtr, colInd,
                               pairPtr, pairs, buf, n);
+}
+int OptAMD_DenseCholesky(long long n, const void* A, const void* b, void* L_out, void* x_out, int isDouble,
+                         long long* info) {
+    if (n < 1 || n > 2000000 || !A || !b || !L_out || !x_out || !info) return -1;
+    const long long r = isDouble ? optamd::dense_cholesky_host<double>(n, (const double*)A, (const double*)b, (double*)L_out, (double*)x_out)
+                                 : optamd::dense_cholesky_host<float>(n, (const float*)A, (const float*)b, (float*)L_out, (float*)x_out);
+    if (r < -1) return -1;
+    *info = r;
+    return 0;
 }
 int OptAMD_GenericDescribe(const char* filename, char* buf, int n) {
     std::string text, out;

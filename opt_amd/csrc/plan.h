@@ -204,6 +204,12 @@ public:
         (void)line;
         return -1;
     }
+    // What LinearSolver("cholesky") did on this plan so far (OptAMD_PlanDirectInfo): 0 and one
+    // line of key=value words; -1 on a plan without the statement.
+    virtual int direct_info(std::string* line) const {
+        (void)line;
+        return -1;
+    }
     // The explicitly formed H = J^T J (NormalMatrix("explicit"), include/opt_amd.h): the same
     // pair of calls for the normal matrix of a plan whose energy has that statement.
     virtual bool normal_matrix_shape(long long* rows, int* dim, long long* nnzb) const {

@@ -291,6 +291,15 @@ struct Parser {
                 if (!spec->normal_matrix.empty()) return fail(i, "a second NormalMatrix (the normal matrix has one form)");
                 spec->normal_matrix = t[a[0].first].text;
                 if (spec->normal_matrix == "explicit") spec->use_preconditioner = spec->block_preconditioner = true;
+            } else if (f == "LinearSolver") {
+                // the Step's linear solver; "cholesky" needs one of the two explicit statements
+                // (checked below, and by the general front end: gen/lua.cpp)
+                args(i + 1, &a);
+                if (!spec->linear_solver.empty()) return fail(i, "a second LinearSolver (a Step has one linear solver)");
+                if (a.size() != 1 || !is_single(a[0], Tk::String) ||
+                    (t[a[0].first].text != "cholesky" && t[a[0].first].text != "pcg"))
+                    return fail(i, "LinearSolver(kind): kind is \"cholesky\" or \"pcg\"");
+                spec->linear_solver = t[a[0].first].text;
             } else if (f == "Exclude") {
                 spec->n_exclude++;
             } else if (f == "ComputedArray") {
@@ -300,6 +309,9 @@ struct Parser {
                 spec->uses_sampled_image = true;
             }
         }
+        if (spec->linear_solver == "cholesky" && spec->reduced_system != "explicit" && spec->normal_matrix != "explicit")
+            return fail(t.size() - 1, "LinearSolver(\"cholesky\"): the file has neither ReducedSystem(\"explicit\") nor "
+                                      "NormalMatrix(\"explicit\") (the factorisation needs the assembled matrix of one of them)");
         return true;
     }
 

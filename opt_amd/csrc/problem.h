@@ -44,6 +44,7 @@ struct ProblemSpec {
     std::vector<std::string> eliminate;  // Eliminate(X, ...): the group's unknowns (generated kernels only)
     std::string reduced_system;          // ReducedSystem(form): "explicit" / "implicit", "" without the statement
     std::string normal_matrix;           // NormalMatrix(form): "explicit" / "matrix_free", "" without the statement
+    std::string linear_solver;           // LinearSolver(kind): "cholesky" / "pcg", "" without the statement
     int n_exclude = 0;
     std::vector<std::string> computed_arrays;
     bool uses_sampled_image = false;

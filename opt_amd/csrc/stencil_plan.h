@@ -3,12 +3,15 @@
 // reference's init / step exactly (API/src/solverGPUGaussNewton.t:1766-2349),
 // including the LM trust-region update and its early exits.
 #pragma once
+#include <cmath>
 #include <cstdint>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <type_traits>
 #include <vector>
 #include "csr.h"
+#include "dense_cholesky.h"
 #include "stencil_driver.h"
 
 namespace optamd {
@@ -348,7 +351,7 @@ public:
         allreduce(rz(0), 1);
         const int* stop = lm_ ? stop_ : nullptr;
         if (mat_) materialize();   // cusparseOuter (:2068): J, J^T (, J^T J) at the current X
-        if (pcg_graph_begin(params, Lit)) {
+        if (!direct_step(Lit) && pcg_graph_begin(params, Lit)) {
             pcg_loop(Lit, stop);
             pcg_graph_end();
         }
@@ -625,6 +628,20 @@ public:
     // is rebuilt by the next step
     int reduced_matrix(void** params, int* rowPtr, int* colInd, void* val) override {
         return explicit_matrix(MatrixForm::Schur, params, rowPtr, colInd, val);
+    }
+    // what LinearSolver("cholesky") did on this plan so far; -1 on a plan without the statement
+    int direct_info(std::string* line) const override {
+        if constexpr (HasExplicitMatrix<Op>::value)
+            if (matrix_ != MatrixForm::None && op_->direct_solver()) {
+                char ratio[40];
+                snprintf(ratio, sizeof(ratio), "%.9g", direct_ratio_);
+                *line = "n=" + std::to_string(direct_n_) + " tiles=" + std::to_string(direct_n_ ? dense_tile_count(direct_n_) : 0) +
+                        " bytes=" + std::to_string(direct_n_ ? dense_bytes(direct_n_, sizeof(T)) : 0) +
+                        " factorisations=" + std::to_string(direct_factorisations_) + " fallbacks=" +
+                        std::to_string(direct_fallbacks_) + " reason=" + direct_reason_ + " min_pivot_ratio=" + ratio;
+                return 0;
+            }
+        return Plan::direct_info(line);
     }
     // what the last symbolic phase of S or H did; -1 on a plan with neither statement
     int symbolic_info(std::string* line) const override {
@@ -922,6 +939,65 @@ private:
                 return true;
             }
         (void)p; (void)Ap; (void)dadd; (void)stop; (void)rs;
+        return false;
+    }
+
+    // LinearSolver("cholesky") (HasExplicitMatrix, Op::direct_solver): in place of the PCG loop, the
+    // assembled matrix (+ LM's diagonal) filled into dense tiles with the retained part of r_ as
+    // the right-hand side, factored and solved into delta_ (dense_cholesky.h). false, with delta_
+    // untouched, where the plan has no such statement, Lit = 0, the storage does not fit
+    // (OPT_AMD_DENSE_MAX_BYTES, default 2 GiB, or the free device memory) or a pivot fails: the
+    // caller then runs the PCG loop, for which everything up to block_init has been done as ever.
+    // The host reads the failure flag once after the factorisation: one 16-byte copy and one
+    // stream sync per Step.
+    bool direct_step(int Lit) {
+        if constexpr (HasExplicitMatrix<Op>::value)
+            if (matrix_ != MatrixForm::None && op_->direct_solver() && Lit > 0) {
+                long long rows = 0, nnzb = 0;
+                int dim = 0;
+                if (!op_->matrix_shape(&rows, &dim, &nnzb) || rows * dim < 1) return false;
+                const long long n = rows * dim;
+                direct_n_ = n;
+                {   // the cap is read at every Step; the free memory counts only while nothing is allocated
+                    const char* cap = getenv("OPT_AMD_DENSE_MAX_BYTES");
+                    const unsigned long long max_bytes = cap && *cap ? strtoull(cap, nullptr, 10) : (2ULL << 30);
+                    const size_t need = dense_bytes(n, sizeof(T));
+                    bool fits = need <= max_bytes;
+                    if (fits && dense_.n() != n) {
+                        dense_.release();
+                        size_t free_b = 0, total_b = 0;
+                        OPT_HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+                        fits = need <= free_b;
+                    }
+                    if (!fits) {
+                        dense_.release();
+                        ++direct_fallbacks_;
+                        direct_reason_ = "memory";
+                        return false;
+                    }
+                    dense_.resize(n);
+                }
+                tbegin("dense_fill");
+                OPT_HIP_CHECK(hipMemsetAsync(dense_.tiles(), 0, sizeof(T) * (size_t)dense_tile_count(n) * kDenseNB * kDenseNB, stream_));
+                dense_.reset(stream_);
+                op_->dense_fill(lm_ ? CtC_ : nullptr, r_, dense_.tiles(), dense_.diag0(), dense_.rhs(), stream_);
+                tend();
+                tbegin("dense_factor"); dense_.factor(stream_); tend();
+                double ratio = INFINITY;
+                if (dense_.status(stream_, &ratio) >= 0) {   // (min_pivot_ratio stays the last completed factorisation's)
+                    ++direct_fallbacks_;
+                    direct_reason_ = "pivot";
+                    return false;
+                }
+                direct_ratio_ = ratio;
+                tbegin("dense_solve");
+                dense_.solve(stream_);
+                op_->dense_store(dense_.solution(), delta_, &dense_.status_dev()->fail, stream_);
+                tend();
+                ++direct_factorisations_;
+                return true;
+            }
+        (void)Lit;
         return false;
     }
 
@@ -1276,6 +1352,10 @@ private:
     T *blk_ = nullptr, *z_ = nullptr;          // its blocks (inverted in place) and z = M^-1 r
     bool schur_ = false;                       // Eliminate: PCG on the Schur complement (HasSchur)
     T *w_ = nullptr, *be_ = nullptr;           // compact (eliminated elements): M^-1-sized products, the stash of b_e
+    DenseFactor<T> dense_;                     // LinearSolver("cholesky"): the tiles, allocated at the first direct Step
+    long long direct_n_ = 0, direct_factorisations_ = 0, direct_fallbacks_ = 0;
+    double direct_ratio_ = INFINITY;
+    const char* direct_reason_ = "none";
     MatrixForm matrix_ = MatrixForm::None;     // S or H assembled per step, the apply a block SpMV (HasExplicitMatrix)
     uint8_t* flags_ = nullptr;
     int* stop_ = nullptr;

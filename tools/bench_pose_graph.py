@@ -18,7 +18,10 @@ iteration (`normal_spmv` for the explicit form, `gen_apply` for the others), `no
 `normal_assemble` per step — the host symbolic phase in ms, the shape and bytes of H, the SpMV's
 bytes (values, column indices, row pointers, p gathered once per block, Ap) over its time against
 the 6.29 TB/s float4 copy rate, and the cost after each of 5 GN steps. A library from before the
-statement (OPT_AMD_LIB) knows only scalar and block.
+statement (OPT_AMD_LIB) knows only scalar and block. The `cholesky` variant
+(energies/direct/pose_graph_2d_cholesky.t) is the direct step: its table adds `dense_fill`,
+`dense_factor`, `dense_solve`, the factorisation's flop rate on n^3 / 3 and direct_info() (at a
+size whose dense storage does not fit: the memory fall-back, and the explicit plan's Step).
 """
 import argparse
 import json
@@ -70,7 +73,8 @@ def run_variants(a):
     block = os.path.join(tempfile.mkdtemp(), "pose_graph_2d_block.t")
     open(block, "w").write(text.replace("UsePreconditioner(true)", 'UsePreconditioner("block")'))
     files = {"scalar": shipped, "block": block,
-             "explicit": os.path.join(ROOT, "energies", "normal_matrix", "pose_graph_2d_explicit.t")}
+             "explicit": os.path.join(ROOT, "energies", "normal_matrix", "pose_graph_2d_explicit.t"),
+             "cholesky": os.path.join(ROOT, "energies", "direct", "pose_graph_2d_cholesky.t")}
     names = [v for v in a.variants.split(",") if v]
     cuda = lambda x: torch.from_numpy(x).cuda()  # noqa: E731
     consts = problems.pose_graph_2d_params(w, cuda)
@@ -112,13 +116,19 @@ def run_variants(a):
             one_step(s)
         table = {}
         for n in ("jtf", "gn_init", "blk_init", "step2", "blk_step2", "step3", "gen_apply", "normal_eblk", "normal_assemble",
-                  "normal_spmv", "update", "cost"):
+                  "normal_spmv", "dense_fill", "dense_factor", "dense_solve", "update", "cost"):
             cnt, ms = s.kernel_stat(n)
             if cnt:
                 table[n] = {"launches": cnt, "us_per_launch": 1e3 * ms / cnt}
         s.set_kernel_timing(0)
         out[k]["kernels"] = table
-        out[k]["apply_us_per_iteration"] = table.get("normal_spmv" if k == "explicit" else "gen_apply", {}).get("us_per_launch", 0.0)
+        out[k]["apply_us_per_iteration"] = table.get("normal_spmv" if k in ("explicit", "cholesky") else "gen_apply", {}).get("us_per_launch", 0.0)
+        if k == "cholesky":
+            n, f = 3 * dims[0], table.get("dense_factor", {}).get("us_per_launch", 0.0)
+            # (min_pivot_ratio is inf before the first factorisation: a string, so the record stays JSON)
+            out[k]["direct_info"] = {a: (v if v == v and abs(v) != float("inf") else str(v)) if isinstance(v, float) else v
+                                     for a, v in s.direct_info().items()}
+            out[k]["factor_TFLOPs"] = n ** 3 / 3 / (f * 1e-6) / 1e12 if f else 0.0
     if "explicit" in solvers:
         # the symbolic phase alone: a fresh plan, its incidence lists built by a cost evaluation
         # first, then the bind-and-pattern call (OptAMD_NormalMatrix without arrays)

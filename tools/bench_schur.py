@@ -19,6 +19,10 @@ energies/bundle_adjustment_schur_explicit.t; same inputs):
   the pattern alone), the shape of S, and the SpMV's bytes (blocks x C^2 x 4) over its time;
 * the cost after each of 5 GN steps at lIterations = 10.
 
+The `cholesky` variant (energies/direct/bundle_adjustment_schur_cholesky.t, not in the default
+set: --variants explicit,cholesky) is the direct step: its table adds `dense_fill`,
+`dense_factor`, `dense_solve`, the factorisation's flop rate on n^3 / 3 and direct_info().
+
 --variants picks a subset (a library from before the statement knows no Schur file: run it
 with OPT_AMD_LIB and --variants scalar,block to alternate two builds in one session).
 --design-table prints the markdown rows for DESIGN §3.6 from the JSON files given.
@@ -78,7 +82,7 @@ def design_table(paths):
     print("| run | variant | GN step ms | apply us / PCG iteration | cost after GN steps 1..5 |")
     print("|---|---|---|---|---|")
     for p, r in zip(paths, runs):
-        for v in ("scalar", "block", "schur", "explicit"):
+        for v in ("scalar", "block", "schur", "explicit", "cholesky"):
             if v in r:
                 print("| %s | %s | %.2f | %.0f | %s |" % (os.path.basename(p), v, r[v]["step_ms_median"], r[v]["apply_us_per_iteration"],
                                                       " ".join("%.5g" % c for c in r[v]["cost_after_steps"][1:])))
@@ -110,7 +114,8 @@ def main():
     block = os.path.join(tempfile.mkdtemp(), "bundle_adjustment_block.t")
     open(block, "w").write(text.replace("UsePreconditioner(true)", 'UsePreconditioner("block")'))
     files = {"scalar": shipped, "block": block, "schur": os.path.join(ROOT, "energies", "bundle_adjustment_schur.t"),
-             "explicit": os.path.join(ROOT, "energies", "bundle_adjustment_schur_explicit.t")}
+             "explicit": os.path.join(ROOT, "energies", "bundle_adjustment_schur_explicit.t"),
+             "cholesky": os.path.join(ROOT, "energies", "direct", "bundle_adjustment_schur_cholesky.t")}
     names = [v for v in args.variants.split(",") if v]
 
     dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
@@ -152,7 +157,8 @@ def main():
             one_step(s)
         table = {}
         for n in ("jtf", "gn_init", "blk_init", "step2", "blk_step2", "step3", "gen_apply", "schur_rhs", "schur_elim",
-                  "schur_apply", "schur_back", "schur_eblk", "schur_assemble", "schur_spmv", "update", "cost"):
+                  "schur_apply", "schur_back", "schur_eblk", "schur_assemble", "schur_spmv", "dense_fill", "dense_factor",
+                  "dense_solve", "update", "cost"):
             cnt, ms = s.kernel_stat(n)
             if cnt:
                 table[n] = {"launches": cnt, "us_per_launch": 1e3 * ms / cnt}
@@ -160,7 +166,13 @@ def main():
         us = lambda n: table.get(n, {}).get("us_per_launch", 0.0)
         out[k]["kernels"] = table
         out[k]["apply_us_per_iteration"] = (us("schur_elim") + us("schur_apply") if k == "schur" else
-                                            us("schur_spmv") if k == "explicit" else us("gen_apply"))
+                                            us("schur_spmv") if k == "explicit" else 0.0 if k == "cholesky" else us("gen_apply"))
+        if k == "cholesky":
+            n = 6 * w["NC"]
+            # (min_pivot_ratio is inf before the first factorisation: a string, so the record stays JSON)
+            out[k]["direct_info"] = {a: (v if v == v and abs(v) != float("inf") else str(v)) if isinstance(v, float) else v
+                                     for a, v in s.direct_info().items()}
+            out[k]["factor_TFLOPs"] = n ** 3 / 3 / (us("dense_factor") * 1e-6) / 1e12 if us("dense_factor") else 0.0
     if "explicit" in solvers:
         # the symbolic phase alone: a fresh plan, its incidence lists built by a cost evaluation
         # first, then the bind-and-pattern call (OptAMD_ReducedMatrix without arrays)

@@ -55,6 +55,7 @@ int main(int argc, char** argv) {
         printf("// dump[%zu]: graph=%d rows=%d nnz=%d\n", i, gs.dump[i].graph, gs.dump[i].rows, gs.dump[i].nnz);
     for (size_t i = 0; i < gs.nb_pairs.size(); ++i)
         printf("// nb_pairs[%zu]: %d %d\n", i, gs.nb_pairs[i].first, gs.nb_pairs[i].second);
+    if (gs.has_dense) printf("// has_dense=1\n");   // LinearSolver("cholesky") (files without it print nothing here)
     // RobustEnergy statements (files without one print nothing here)
     for (size_t g = 0; g < m.loss.size(); ++g) {
         const optamd::gen::GLossGroup& L = m.loss[g];
