@@ -190,6 +190,7 @@ int OptAMD_PlanSymbolicInfo(Opt_Plan* plan, char* buf, int buflen);
  * original diagonal entry (reason=pivot; the host reads the flag once per Step after the
  * factorisation). One line of key=value words in buf:
  *   n=N tiles=N bytes=N factorisations=N fallbacks=N reason=none|memory|pivot min_pivot_ratio=X
+ *   covariances=N cov_bytes=N                                   (OptAMD_Covariance, below)
  * n the padded-free dimension, tiles the stored 64 x 64 tiles, bytes the dense storage,
  * factorisations / fallbacks the Steps that took either path, reason the last fall-back's,
  * min_pivot_ratio the smallest pivot / original diagonal of the last completed factorisation (inf before
@@ -246,6 +247,36 @@ int OptAMD_NormalPatternDevice(long long nVertices, int nLists, const int* const
  * or -1 for invalid arguments or a matrix whose storage does not fit the device. */
 int OptAMD_DenseCholesky(long long n, const void* A, const void* b, void* L_out, void* x_out, int isDouble,
                          long long* info);
+
+/* Marginal covariances: selected blockDim x blockDim blocks of A^-1, A the plan's assembled S or
+ * H at the bound unknowns WITHOUT LM's diagonal (on an LM plan with Eliminate the eliminated
+ * blocks are inverted undamped too), from the dense Cholesky factor of LinearSolver("cholesky").
+ * The call binds the arrays, assembles the matrix as OptAMD_NormalMatrix / OptAMD_ReducedMatrix
+ * do (robust terms with their weights), fills and factors the tiles the direct Step uses, and
+ * forms Y = L^-1 E for the identity columns E of the selected unknowns by a forward launch chain
+ * of MFMA tile products, then block (s, t) = Y_s^T Y_t. Work and storage follow the selection:
+ * tiles of Y left of an element's first unknown are never formed. rowElem / colElem are host
+ * arrays of nPairs element numbers, numbered as the block rows of OptAMD_PlanNormalMatrixShape /
+ * OptAMD_PlanReducedMatrixShape; blocks is a device array blocks[nPairs][blockDim][blockDim] in
+ * the plan's precision. Blocks of an excluded or held element, and its cross blocks, are zeros.
+ * The call leaves the unknowns, the cost, the LM state and the next Step (bitwise) as they were.
+ * Returns 0; -1 for NULL or an element out of range; 1 on a plan without LinearSolver("cholesky");
+ * 2 when the tiles plus the selection's workspace exceed OPT_AMD_DENSE_MAX_BYTES (read at each
+ * call) or the free device memory (reason=memory: no fall-back, no chunking); 3 when a pivot
+ * fails (reason=pivot: gauge freedom; blocks untouched). OptAMD_PlanError holds the message, for
+ * a pivot with the row, the element and the channel. OptAMD_PlanDirectInfo's line ends in
+ * covariances=N cov_bytes=N: the calls completed and the last workspace. */
+int OptAMD_Covariance(Opt_State* state, Opt_Plan* plan, void** problemparams, long long nPairs, const int* rowElem,
+                      const int* colElem, void* blocks);
+
+/* The same kernels with no plan: blocks of A^-1 for a host matrix A (n x n, row-major, symmetric
+ * positive definite; float, or double with isDouble != 0) cut into elements of C unknowns (n a
+ * multiple of C, 1 <= C <= 64). rowElem / colElem and out[nPairs][C][C] are host arrays. *info is
+ * -1, the first row whose pivot failed (out untouched), or -2 when the storage does not fit the
+ * device. Returns 0, or -1 for invalid arguments (an element out of range among them), before
+ * any launch. */
+int OptAMD_DenseInverseBlocks(long long n, const void* A, int C, long long nPairs, const int* rowElem, const int* colElem,
+                              void* out, int isDouble, long long* info);
 
 /* Ap = J^T J p at the current unknowns (+ CtC*p for LM plans, with the CtC of the
  * last LM step) and *p_dot_Ap = p.Ap (reference kernels.PCGStep1,
@@ -321,7 +352,9 @@ int OptAMD_CommKind(OptAMD_Comm* comm, char* buf, int buflen);
 /* The error that stopped the last Init / Step of this plan (a problem found only when
  * the arrays were bound, e.g. an arap graph whose adjacency exceeds 2^31 slots), copied
  * into buf; returns its length, 0 when there was none (-1 for NULL). After such an
- * error Opt_ProblemStep returns 0 and Opt_ProblemCurrentCost NaN; the process goes on. */
+ * error Opt_ProblemStep returns 0 and Opt_ProblemCurrentCost NaN; the process goes on.
+ * Where there is none, the refusal of the last OptAMD_Covariance (reason=memory, reason=pivot, a
+ * bad index, no statement), which stops nothing and which the next Init or Step clears. */
 int OptAMD_PlanError(Opt_Plan* plan, char* buf, int buflen);
 /* All ranks as threads of one process (shared device or peer devices): for testing
  * the decomposition on one GPU. The rank handles belong to the group. */

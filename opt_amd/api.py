@@ -130,6 +130,9 @@ _SIGNATURES = [
                                                   ctypes.c_int]),
     ("OptAMD_DenseCholesky", ctypes.c_int, [ctypes.c_longlong, _VP, _VP, _VP, _VP, ctypes.c_int,
                                             ctypes.POINTER(ctypes.c_longlong)]),
+    ("OptAMD_Covariance", ctypes.c_int, [_VP, _VP, ctypes.POINTER(_VP), ctypes.c_longlong, _VP, _VP, _VP]),
+    ("OptAMD_DenseInverseBlocks", ctypes.c_int, [ctypes.c_longlong, _VP, ctypes.c_int, ctypes.c_longlong, _VP, _VP, _VP,
+                                                 ctypes.c_int, ctypes.POINTER(ctypes.c_longlong)]),
     ("OptAMD_GenericCompileCheck", ctypes.c_int, [ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]),
     ("OptAMD_GenericForms", ctypes.c_int, [ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]),
 ]
@@ -432,13 +435,50 @@ class OptSolver:
     def direct_info(self):
         """What LinearSolver("cholesky") did on this plan so far (OptAMD_PlanDirectInfo): a dict
         with n, tiles, bytes, factorisations, fallbacks (ints), reason ('none', 'memory' or
-        'pivot': the last fall-back's) and min_pivot_ratio (float, of the last factorisation);
+        'pivot': the last fall-back's), min_pivot_ratio (float, of the last factorisation),
+        covariances (covariance() calls completed) and cov_bytes (the last call's workspace);
         None on a plan without the statement."""
         buf = ctypes.create_string_buffer(256)
         if self.lib.OptAMD_PlanDirectInfo(self.plan, buf, 256) < 0:
             return None
         kv = dict(w.split("=", 1) for w in buf.value.decode().split())
         return {k: (v if k == "reason" else float(v) if k == "min_pivot_ratio" else int(v)) for k, v in kv.items()}
+
+    def covariance(self, problem_params, elements=None, pairs=None):
+        """Marginal covariance blocks at the bound unknowns (OptAMD_Covariance): C x C blocks of the
+        inverse of the plan's assembled S or H, without LM's diagonal, from the dense Cholesky
+        factor of LinearSolver("cholesky"). Default: the diagonal block of every retained
+        element; `elements` selects diagonal blocks; `pairs` is a (K, 2) list of (row element,
+        column element), numbered as the block rows of normal_matrix() / reduced_matrix().
+        Returns a numpy array (K, C, C) in the plan's precision; blocks of excluded or held
+        elements are zeros. ValueError on a plan without the statement or a bad index,
+        MemoryError when tiles + workspace exceed OPT_AMD_DENSE_MAX_BYTES or the free memory,
+        numpy.linalg.LinAlgError (with the row) when a pivot fails."""
+        import numpy as np
+        import torch
+        if self.direct_info() is None:
+            raise ValueError('covariance() needs LinearSolver("cholesky") in the energy file, beside '
+                             'ReducedSystem("explicit") or NormalMatrix("explicit")')
+        pk = ParamPack(problem_params)
+        shape = None
+        for fn, get in (("OptAMD_NormalMatrix", self.normal_matrix_shape), ("OptAMD_ReducedMatrix", self.reduced_matrix_shape)):
+            if getattr(self.lib, fn)(self.plan, pk.ptr, None, None, None) == 0:   # binds and builds the pattern
+                shape = get()
+                break
+        if shape is None:
+            self._raise_plan_error()
+            raise OptError("covariance: the plan has no assembled matrix")
+        rows, dim, _ = shape
+        r, c = _block_selection(rows, elements, pairs)
+        out = torch.empty((max(len(r), 1), dim, dim), dtype=torch.float64 if self.double_precision else torch.float32,
+                          device="cuda")
+        e = self.lib.OptAMD_Covariance(self.state, self.plan, pk.ptr, len(r), r.ctypes.data, c.ctypes.data, _ptr(out))
+        if e:
+            buf = ctypes.create_string_buffer(512)
+            self.lib.OptAMD_PlanError(self.plan, buf, 512)
+            msg = buf.value.decode() or "OptAMD_Covariance failed"
+            raise {1: ValueError, 2: MemoryError, 3: np.linalg.LinAlgError}.get(e, OptError)(msg)
+        return out[:len(r)].cpu().numpy()
 
     def normal_matrix_shape(self):
         """(block rows, block dimension, blocks) of the explicitly formed H = J^T J once the
@@ -734,6 +774,51 @@ def dense_cholesky(A, b, L=None, x=None):
                                            int(dt == np.float64), ctypes.byref(info)):
         raise OptError("OptAMD_DenseCholesky: invalid arguments, or the matrix does not fit the device")
     return L, x, int(info.value)
+
+
+def _block_selection(n_elements, elements, pairs):
+    """(row elements, column elements) as int32 arrays for covariance() / dense_inverse_blocks():
+    `pairs` (K, 2), else the diagonal blocks of `elements`, else of every element. ValueError on
+    an index outside [0, n_elements)."""
+    import numpy as np
+    if pairs is not None and elements is not None:
+        raise ValueError("give elements or pairs, not both")
+    if pairs is not None:
+        pq = np.asarray(pairs, np.int64).reshape(-1, 2)
+    else:
+        e = np.arange(n_elements) if elements is None else np.asarray(elements, np.int64).reshape(-1)
+        pq = np.stack([e, e], axis=1)
+    if pq.size and (pq.min() < 0 or pq.max() >= n_elements):
+        raise ValueError(f"element index out of range: the matrix has {n_elements} elements")
+    return np.ascontiguousarray(pq[:, 0], np.int32), np.ascontiguousarray(pq[:, 1], np.int32)
+
+
+def dense_inverse_blocks(A, C, elements=None, pairs=None, out=None):
+    """Blocks of A^-1 on the device from the dense Cholesky factor (OptAMD_DenseInverseBlocks; the
+    kernels behind OptSolver.covariance): A (n x n, symmetric positive definite, float32 or
+    float64 numpy) cut into elements of C unknowns. The selection as in covariance(). Returns
+    (blocks (K, C, C), info): info is -1, or the first row whose pivot failed, and then blocks (the
+    caller's `out` where given, else zeros) is untouched. ValueError for n no multiple of C or an
+    index out of range, before any launch; MemoryError when the storage does not fit the device."""
+    import numpy as np
+    dt = np.float64 if np.asarray(A).dtype == np.float64 else np.float32
+    A = np.ascontiguousarray(A, dt)
+    n = A.shape[0]
+    if A.ndim != 2 or A.shape != (n, n) or n < 1:
+        raise ValueError("dense_inverse_blocks: A must be n x n, n >= 1")
+    if not 1 <= C <= 64 or n % C:
+        raise ValueError(f"dense_inverse_blocks: n = {n} must be a multiple of C = {C}, 1 <= C <= 64")
+    r, c = _block_selection(n // C, elements, pairs)
+    out = np.zeros((len(r), C, C), dt) if out is None else out
+    if out.dtype != dt or out.shape != (len(r), C, C) or not out.flags.c_contiguous:
+        raise ValueError("dense_inverse_blocks: out must be a contiguous (K, C, C) array of A's dtype")
+    info = ctypes.c_longlong(-1)
+    if load_library().OptAMD_DenseInverseBlocks(n, A.ctypes.data, C, len(r), r.ctypes.data, c.ctypes.data, out.ctypes.data,
+                                                int(dt == np.float64), ctypes.byref(info)):
+        raise ValueError("OptAMD_DenseInverseBlocks: invalid arguments")
+    if info.value == -2:
+        raise MemoryError("OptAMD_DenseInverseBlocks: the tiles and the selection's workspace do not fit the device")
+    return out, int(info.value)
 
 
 def problem_family(energy_file: str, solver_kind: str = "gaussNewtonGPU") -> str:

@@ -22,6 +22,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstddef>
+#include <vector>
 
 namespace optamd {
 
@@ -43,6 +44,38 @@ struct DenseStatus {
     int pad;
     double ratio;   // smallest pivot / original diagonal entry met so far
 };
+
+// Blocks of A^-1 from the factor (DenseFactor::covariance): A^-1 = L^-T L^-1, so the C x C block
+// (s, t) is Y_s^T Y_t with Y = L^-1 E and E the identity columns of the selected unknowns. The
+// right-hand sides are stored transposed, X = Y^T: one row per selected unknown, n columns, in
+// 64 x 64 tiles X(R, I), tile-row R major. The distinct selected elements are sorted ascending and
+// packed floor(64 / C) to a tile-row (unused rows zero), so no element straddles two tile-rows and
+// every requested block lies inside one Gram tile G(R, R') = sum_I X(R, I) X(R', I)^T. X(R, I) is
+// identically zero for I < start(R) = floor(first selected unknown of R / 64): those tiles are
+// never written, read or multiplied. start is non-decreasing in R, so the tile-rows live at panel
+// k are the prefix R < live(k).
+//
+// Forward chain, right-looking, two launches per panel k over the live prefix: the diagonal step
+// X(R, k) <- X(R, k) L_kk^-T (the dense_panel shape) and the trailing step X(R, I) -= X(R, k)
+// L(I, k)^T, I > k (the dense_update shape). Then one Gram workgroup per needed (R, R'), its sum
+// over I ascending from max(start(R), start(R')), and a gather of the requested blocks. The
+// selection is laid out on the host, once per call.
+struct DenseSelection {
+    // elements of C unknowns each, 64 % C need not be 0, 1 <= C <= 64; every index in [0, n / C).
+    // false (nothing built) on a bad index, C out of range or n no multiple of C.
+    bool build(long long n, int C, long long nPairs, const int* rowElem, const int* colElem);
+    long long n = 0, nt = 0, nPairs = 0, tile_rows = 0, gram_tiles = 0, x_tiles = 0;
+    int C = 0;
+    std::vector<int> unknown;     // tile_rows x 64: the unknown of each row of X, -1 where unused
+    std::vector<int> start;       // per tile-row
+    std::vector<int> live;        // per panel: tile-rows with start <= k
+    std::vector<int> gramR, gramC;   // per Gram tile: its two tile-rows
+    std::vector<int> blk;         // per requested block: Gram tile, first row, first column, row element, column element
+    // flops of the forward chain (2 * 64^3 per tile product)
+    double forward_flops() const;
+};
+// what DenseFactor<T>::covariance allocates for a selection, beside dense_bytes
+size_t dense_cov_bytes(const DenseSelection& sel, size_t elem);
 
 template <typename T>
 class DenseFactor {
@@ -68,6 +101,19 @@ public:
     void solve(hipStream_t s);
     // one small copy and one stream sync: the failing row or -1, the smallest pivot ratio
     int status(hipStream_t s, double* min_ratio);
+    // Blocks of A^-1 after factor() (DenseSelection above): out[q][C][C] on the device for request
+    // q. mask (may be null): one value per unknown, 0 marks an unknown whose blocks and cross
+    // blocks are returned as zeros. covariance() is the three stages in order; a plan brackets
+    // them with its timer. The workspace is sized by cov_begin and freed with the factor.
+    void covariance(const DenseSelection& sel, const T* mask, T* out, hipStream_t s) {
+        cov_begin(sel, s);
+        cov_forward(sel, s);
+        cov_gram(sel, mask, out, s);
+    }
+    void cov_begin(const DenseSelection& sel, hipStream_t s);     // workspace, the layout uploaded, the seed
+    void cov_forward(const DenseSelection& sel, hipStream_t s);
+    void cov_gram(const DenseSelection& sel, const T* mask, T* out, hipStream_t s);   // Gram tiles and gather
+    size_t cov_capacity() const { return ws_bytes_; }
     // the factor as a device row-major n x n matrix (lower triangle written, padding dropped)
     void extract_lower(T* L, hipStream_t s) const;
 
@@ -81,6 +127,8 @@ private:
     long long n_ = 0, nt_ = 0;
     T *tiles_ = nullptr, *inv_ = nullptr, *diag0_ = nullptr, *rhs_ = nullptr;
     DenseStatus* st_ = nullptr;
+    char* ws_ = nullptr;          // covariance workspace: X, the Gram tiles, the selection's index arrays
+    size_t ws_bytes_ = 0;
 };
 
 // Host arrays in, host arrays out (OptAMD_DenseCholesky): fill, factor and solve on the current
@@ -88,5 +136,11 @@ private:
 // storage does not fit the device.
 template <typename T>
 long long dense_cholesky_host(long long n, const T* A, const T* b, T* L, T* x);
+
+// Host arrays in, host array out (OptAMD_DenseInverseBlocks): fill, factor and covariance() for a
+// selection built by the caller. Returns the first failing row (out untouched) or -1; -2 where
+// the storage does not fit the device.
+template <typename T>
+long long dense_inverse_blocks_host(long long n, const T* A, const DenseSelection& sel, T* out);
 
 }  // namespace optamd

@@ -1,9 +1,12 @@
 // dense_cholesky.hip — the kernels and launch chains of dense_cholesky.h.
 #include "dense_cholesky.h"
 
+#include <algorithm>
 #include <cfloat>
 #include <cmath>
 #include <limits>
+#include <utility>
+#include <vector>
 
 #include "common.h"
 
@@ -286,7 +289,156 @@ __global__ __launch_bounds__(NB) void dense_backward_kernel(const T* __restrict_
     b[(long long)K * NB + t] = bi;
 }
 
+// ---- blocks of A^-1 (DenseSelection in dense_cholesky.h) ----
+// X(R, I) of the transposed right-hand sides
+__device__ __forceinline__ long long cov_tile(long long R, long long I, int nt) { return (R * nt + I) * (long long)kTile; }
+
+// Seed, one workgroup per tile (I, R) with I >= start(R): zero, then the one of each selected
+// unknown of the tile-row that falls into panel I (written by the thread that zeroed the row's
+// entries or another: the barrier between orders them).
+template <typename T>
+__global__ __launch_bounds__(256) void dense_cov_seed_kernel(T* __restrict__ X, const int* __restrict__ unknown,
+                                                             const int* __restrict__ start, int nt, const DenseStatus* st) {
+    if (st->fail >= 0) return;
+    const int I = (int)blockIdx.x, R = (int)blockIdx.y;
+    if (I < start[R]) return;
+    T* x = X + cov_tile(R, I, nt);
+    for (int e = threadIdx.x; e < kTile; e += 256) x[e] = (T)0;
+    __syncthreads();
+    if (threadIdx.x < NB) {
+        const int g = unknown[R * NB + (int)threadIdx.x];
+        if (g >= 0 && (g >> 6) == I) x[(int)threadIdx.x * NB + (g & 63)] = (T)1;
+    }
+}
+
+// Diagonal step of panel k: X(R, k) <- X(R, k) L_kk^-T for the live tile-row R = blockIdx.x
+template <typename T>
+__global__ __launch_bounds__(256) void dense_cov_diag_kernel(T* X, const T* __restrict__ invk, int k, int nt, const DenseStatus* st) {
+    if (st->fail >= 0) return;
+    __shared__ T As[NB][kKC + 1], Bs[NB][kKC + 1];
+    T* A = X + cov_tile(blockIdx.x, k, nt);
+    Frag16<T> f;
+    f.zero();
+    tile_abt<T, false>(A, invk, As, Bs, f);
+    f.store(A);
+}
+
+// Trailing step of panel k: X(R, I) -= X(R, k) L(I, k)^T for I = k + 1 + blockIdx.x, R = blockIdx.y
+template <typename T>
+__global__ __launch_bounds__(256) void dense_cov_trail_kernel(T* X, const T* __restrict__ tiles, int k, int nt, const DenseStatus* st) {
+    if (st->fail >= 0) return;
+    __shared__ T As[NB][kKC + 1], Bs[NB][kKC + 1];
+    const int I = k + 1 + (int)blockIdx.x, R = (int)blockIdx.y;
+    T* C = X + cov_tile(R, I, nt);
+    Frag16<T> f;
+    f.load(C);
+    tile_abt<T, true>(X + cov_tile(R, k, nt), tiles + dense_tile(I, k), As, Bs, f);
+    f.store(C);
+}
+
+// Gram tile p = (R, R'): sum over I of X(R, I) X(R', I)^T, I ascending from the later start
+template <typename T>
+__global__ __launch_bounds__(256) void dense_cov_gram_kernel(const T* __restrict__ X, const int* __restrict__ start,
+                                                             const int* __restrict__ gramR, const int* __restrict__ gramC,
+                                                             T* __restrict__ G, int nt, const DenseStatus* st) {
+    if (st->fail >= 0) return;
+    __shared__ T As[NB][kKC + 1], Bs[NB][kKC + 1];
+    const int R = gramR[blockIdx.x], Rc = gramC[blockIdx.x];
+    Frag16<T> f;
+    f.zero();
+    for (int I = max(start[R], start[Rc]); I < nt; ++I)
+        tile_abt<T, false>(X + cov_tile(R, I, nt), X + cov_tile(Rc, I, nt), As, Bs, f);
+    f.store(G + (long long)blockIdx.x * kTile);
+}
+
+// Requested block q out of its Gram tile, one thread per entry; zeros where the mask holds a 0
+// for either element.
+template <typename T>
+__global__ __launch_bounds__(256) void dense_cov_gather_kernel(const T* __restrict__ G, const int* __restrict__ blk, int C,
+                                                               long long nPairs, const T* __restrict__ mask,
+                                                               T* __restrict__ out, const DenseStatus* st) {
+    if (st->fail >= 0) return;
+    const long long CC = (long long)C * C, total = nPairs * CC;
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
+        const long long q = e / CC;
+        const int ij = (int)(e - q * CC), i = ij / C, j = ij - i * C;
+        const int* b = blk + q * 5;
+        const bool on = !mask || (mask[(long long)b[3] * C] != (T)0 && mask[(long long)b[4] * C] != (T)0);
+        out[e] = on ? G[(long long)b[0] * kTile + (b[1] + i) * NB + b[2] + j] : (T)0;
+    }
+}
+
+size_t cov_align(size_t b) { return (b + 255) & ~(size_t)255; }
+
 }  // namespace
+
+bool DenseSelection::build(long long n_, int C_, long long nPairs_, const int* rowElem, const int* colElem) {
+    // (n: the grids of the seed and the trailing step stay below 65536 a side)
+    if (n_ < 1 || n_ > 2000000 || C_ < 1 || C_ > NB || n_ % C_ != 0 || nPairs_ < 0 || (nPairs_ > 0 && (!rowElem || !colElem))) return false;
+    const long long ne = n_ / C_;
+    for (long long q = 0; q < nPairs_; ++q)
+        if (rowElem[q] < 0 || rowElem[q] >= ne || colElem[q] < 0 || colElem[q] >= ne) return false;
+    n = n_, C = C_, nPairs = nPairs_, nt = dense_tiles_per_side(n_);
+    std::vector<char> sel((size_t)ne, 0);
+    for (long long q = 0; q < nPairs; ++q) sel[rowElem[q]] = sel[colElem[q]] = 1;
+    std::vector<int> slot((size_t)ne, -1);   // element -> its place in the sorted selection
+    const int per = NB / C;
+    long long m = 0;
+    unknown.clear();
+    start.clear();
+    for (long long e = 0; e < ne; ++e) {
+        if (!sel[e]) continue;
+        if (m % per == 0) {
+            unknown.insert(unknown.end(), NB, -1);
+            start.push_back((int)(e * C / NB));
+        }
+        for (int i = 0; i < C; ++i) unknown[(m / per) * NB + (m % per) * C + i] = (int)(e * C + i);
+        slot[e] = (int)m++;
+    }
+    tile_rows = (long long)start.size();
+    x_tiles = tile_rows * nt;
+    live.assign((size_t)nt, 0);
+    for (long long k = 0, R = 0; k < nt; ++k) {
+        while (R < tile_rows && start[R] <= k) ++R;
+        live[k] = (int)R;
+    }
+    gramR.clear();
+    gramC.clear();
+    blk.assign((size_t)nPairs * 5, 0);
+    std::vector<std::pair<long long, long long>> order((size_t)nPairs);   // (tile-row pair, request), to number the distinct pairs
+    for (long long q = 0; q < nPairs; ++q)
+        order[q] = {(long long)(slot[rowElem[q]] / per) * tile_rows + slot[colElem[q]] / per, q};
+    std::sort(order.begin(), order.end());
+    for (long long o = 0; o < nPairs; ++o) {
+        const long long q = order[o].second;
+        if (o == 0 || order[o].first != order[o - 1].first) {
+            gramR.push_back((int)(order[o].first / tile_rows));
+            gramC.push_back((int)(order[o].first % tile_rows));
+        }
+        int* b = &blk[q * 5];
+        b[0] = (int)gramR.size() - 1;
+        b[1] = (slot[rowElem[q]] % per) * C;
+        b[2] = (slot[colElem[q]] % per) * C;
+        b[3] = rowElem[q];
+        b[4] = colElem[q];
+    }
+    gram_tiles = (long long)gramR.size();
+    return true;
+}
+
+double DenseSelection::forward_flops() const {
+    double products = 0;
+    for (long long R = 0; R < tile_rows; ++R) {
+        const double m = (double)(nt - start[R]);
+        products += m * (m + 1) / 2;   // one diagonal and nt - k - 1 trailing products per live panel
+    }
+    return products * 2.0 * NB * NB * NB;
+}
+
+size_t dense_cov_bytes(const DenseSelection& sel, size_t elem) {
+    return cov_align((size_t)sel.x_tiles * kTile * elem) + cov_align((size_t)sel.gram_tiles * kTile * elem) +
+           cov_align(sizeof(int) * (sel.unknown.size() + sel.start.size() + sel.gramR.size() + sel.gramC.size() + sel.blk.size() + 1));
+}
 
 size_t dense_bytes(long long n, size_t elem) {
     const long long nt = dense_tiles_per_side(n);
@@ -301,6 +453,9 @@ void DenseFactor<T>::release() {
     }
     dfree(st_);
     st_ = nullptr;
+    dfree(ws_);
+    ws_ = nullptr;
+    ws_bytes_ = 0;
     n_ = nt_ = 0;
 }
 
@@ -367,6 +522,69 @@ void DenseFactor<T>::extract_lower(T* L, hipStream_t s) const {
     OPT_HIP_CHECK(hipGetLastError());
 }
 
+namespace {
+// the parts of the covariance workspace, in the order dense_cov_bytes sums them
+template <typename T>
+struct CovParts {
+    T *X, *G;
+    int *unknown, *start, *gramR, *gramC, *blk;
+    CovParts(char* ws, const DenseSelection& sel) {
+        X = (T*)ws;
+        G = (T*)(ws + cov_align((size_t)sel.x_tiles * kTile * sizeof(T)));
+        unknown = (int*)((char*)G + cov_align((size_t)sel.gram_tiles * kTile * sizeof(T)));
+        start = unknown + sel.unknown.size();
+        gramR = start + sel.start.size();
+        gramC = gramR + sel.gramR.size();
+        blk = gramC + sel.gramC.size();
+    }
+};
+}  // namespace
+
+template <typename T>
+void DenseFactor<T>::cov_begin(const DenseSelection& sel, hipStream_t s) {
+    const size_t need = dense_cov_bytes(sel, sizeof(T));
+    if (need != ws_bytes_) {
+        dfree(ws_);
+        ws_ = nullptr;
+        ws_bytes_ = 0;
+        ws_ = (char*)dmalloc(need);
+        ws_bytes_ = need;
+    }
+    if (sel.nPairs == 0) return;
+    const CovParts<T> w(ws_, sel);
+    for (auto cp : {std::make_pair(w.unknown, &sel.unknown), std::make_pair(w.start, &sel.start), std::make_pair(w.gramR, &sel.gramR),
+                    std::make_pair(w.gramC, &sel.gramC), std::make_pair(w.blk, &sel.blk)})
+        OPT_HIP_CHECK(hipMemcpyAsync(cp.first, cp.second->data(), sizeof(int) * cp.second->size(), hipMemcpyHostToDevice, s));
+    OPT_HIP_CHECK(hipStreamSynchronize(s));   // (the selection's vectors are the caller's again)
+    dense_cov_seed_kernel<T><<<dim3((unsigned)nt_, (unsigned)sel.tile_rows), 256, 0, s>>>(w.X, w.unknown, w.start, (int)nt_, st_);
+    OPT_HIP_CHECK(hipGetLastError());
+}
+
+template <typename T>
+void DenseFactor<T>::cov_forward(const DenseSelection& sel, hipStream_t s) {
+    if (sel.nPairs == 0) return;
+    const CovParts<T> w(ws_, sel);
+    const int nt = (int)nt_;
+    for (int k = 0; k < nt; ++k) {
+        const int live = sel.live[k];
+        if (live == 0) continue;
+        dense_cov_diag_kernel<T><<<live, 256, 0, s>>>(w.X, inv_ + (long long)k * kTile, k, nt, st_);
+        if (nt - k - 1 > 0) dense_cov_trail_kernel<T><<<dim3(nt - k - 1, live), 256, 0, s>>>(w.X, tiles_, k, nt, st_);
+    }
+    OPT_HIP_CHECK(hipGetLastError());
+}
+
+template <typename T>
+void DenseFactor<T>::cov_gram(const DenseSelection& sel, const T* mask, T* out, hipStream_t s) {
+    if (sel.nPairs == 0) return;
+    const CovParts<T> w(ws_, sel);
+    dense_cov_gram_kernel<T><<<(unsigned)sel.gram_tiles, 256, 0, s>>>(w.X, w.start, w.gramR, w.gramC, w.G, (int)nt_, st_);
+    const long long total = sel.nPairs * sel.C * sel.C;
+    dense_cov_gather_kernel<T><<<(unsigned)std::min<long long>((total + 255) / 256, 1 << 16), 256, 0, s>>>(w.G, w.blk, sel.C, sel.nPairs,
+                                                                                                        mask, out, st_);
+    OPT_HIP_CHECK(hipGetLastError());
+}
+
 template class DenseFactor<float>;
 template class DenseFactor<double>;
 
@@ -402,5 +620,38 @@ long long dense_cholesky_host(long long n, const T* A, const T* b, T* L, T* x) {
 }
 template long long dense_cholesky_host<float>(long long, const float*, const float*, float*, float*);
 template long long dense_cholesky_host<double>(long long, const double*, const double*, double*, double*);
+
+template <typename T>
+long long dense_inverse_blocks_host(long long n, const T* A, const DenseSelection& sel, T* out) {
+    const size_t dense = sizeof(T) * (size_t)n * (size_t)n, vec = sizeof(T) * (size_t)n;
+    const size_t blocks = sizeof(T) * (size_t)sel.nPairs * sel.C * sel.C;
+    size_t free_b = 0, total_b = 0;
+    OPT_HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+    if (dense_bytes(n, sizeof(T)) + dense_cov_bytes(sel, sizeof(T)) + dense + vec + blocks > free_b) return -2;
+    T* dA = (T*)dmalloc(dense);
+    T* db = (T*)dmalloc(vec);
+    T* dout = (T*)dmalloc(blocks ? blocks : sizeof(T));
+    OPT_HIP_CHECK(hipMemcpy(dA, A, dense, hipMemcpyHostToDevice));
+    OPT_HIP_CHECK(hipMemset(db, 0, vec));
+    long long fail;
+    {
+        DenseFactor<T> F;
+        F.resize(n);
+        F.fill_from_dense(dA, db, nullptr);
+        F.factor(nullptr);
+        fail = F.status(nullptr, nullptr);
+        if (fail < 0) {
+            F.covariance(sel, nullptr, dout, nullptr);
+            if (blocks) OPT_HIP_CHECK(hipMemcpy(out, dout, blocks, hipMemcpyDeviceToHost));
+        }
+        OPT_HIP_CHECK(hipDeviceSynchronize());
+    }
+    dfree(dA);
+    dfree(db);
+    dfree(dout);
+    return fail;
+}
+template long long dense_inverse_blocks_host<float>(long long, const float*, const DenseSelection&, float*);
+template long long dense_inverse_blocks_host<double>(long long, const double*, const DenseSelection&, double*);
 
 }  // namespace optamd

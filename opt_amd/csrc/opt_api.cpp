@@ -32,6 +32,7 @@ struct Opt_Problem {
 struct Opt_Plan {
     std::unique_ptr<optamd::Plan> impl;
     std::string error;   // set when Init / Step met an optamd::PlanError; the solve stops
+    std::string refusal; // why the last OptAMD_Covariance returned non-zero (the solve goes on); Init / Step clear it
 };
 
 namespace {
@@ -189,6 +190,7 @@ void Opt_SetSolverParameter(Opt_State* state, Opt_Plan* plan, const char* name, 
 void Opt_ProblemInit(Opt_State* state, Opt_Plan* plan, void** problemparams) {
     if (!valid_state(state, "Opt_ProblemInit") || !valid_plan(plan, "Opt_ProblemInit")) exit(1);
     plan->error.clear();
+    plan->refusal.clear();
     guarded(plan, "Opt_ProblemInit", 0, [&] {
         plan->impl->init(problemparams);
         return 0;
@@ -198,6 +200,7 @@ void Opt_ProblemInit(Opt_State* state, Opt_Plan* plan, void** problemparams) {
 int Opt_ProblemStep(Opt_State* state, Opt_Plan* plan, void** problemparams) {
     if (!valid_state(state, "Opt_ProblemStep") || !valid_plan(plan, "Opt_ProblemStep")) exit(1);
     if (!plan->error.empty()) return 0;
+    plan->refusal.clear();
     return guarded(plan, "Opt_ProblemStep", 0, [&] { return plan->impl->step(problemparams); });
 }
 
@@ -396,7 +399,7 @@ void OptAMD_CommDestroy(OptAMD_Comm* comm) {
 int OptAMD_CommSize(OptAMD_Comm* comm) { return comm ? comm->impl->size() : -1; }
 int OptAMD_CommRank(OptAMD_Comm* comm) { return comm ? comm->impl->rank() : -1; }
 int OptAMD_PlanError(Opt_Plan* plan, char* buf, int n) {
-    return valid_plan(plan, "OptAMD_PlanError") ? copy_name(plan->error, buf, n) : -1;
+    return valid_plan(plan, "OptAMD_PlanError") ? copy_name(plan->error.empty() ? plan->refusal : plan->error, buf, n) : -1;
 }
 int OptAMD_CommKind(OptAMD_Comm* comm, char* buf, int n) { return comm ? copy_name(comm->impl->kind(), buf, n) : -1; }
 OptAMD_LocalGroup* OptAMD_LocalGroupCreate(int nranks) {
@@ -643,6 +646,31 @@ int OptAMD_DenseCholesky(long long n, const void* A, const void* b, void* L_out,
                                  : optamd::dense_cholesky_host<float>(n, (const float*)A, (const float*)b, (float*)L_out, (float*)x_out);
     if (r < -1) return -1;
     *info = r;
+    return 0;
+}
+int OptAMD_Covariance(Opt_State* state, Opt_Plan* plan, void** params, long long nPairs, const int* rowElem,
+                      const int* colElem, void* blocks) {
+    if (!valid_state(state, "OptAMD_Covariance") || !valid_plan(plan, "OptAMD_Covariance")) return -1;
+    plan->error.clear();
+    plan->refusal.clear();
+    if (nPairs < 0 || (nPairs > 0 && (!rowElem || !colElem || !blocks))) {
+        plan->refusal = "OptAMD_Covariance: NULL array";
+        return -1;
+    }
+    std::string why;
+    const int r = guarded(plan, "OptAMD_Covariance", -1,
+                          [&] { return plan->impl->covariance(params, nPairs, rowElem, colElem, blocks, &why); });
+    if (r == 1) plan->refusal = "OptAMD_Covariance: the plan's energy has no LinearSolver(\"cholesky\") statement";
+    else if (r != 0 && !why.empty()) plan->refusal = why;
+    return r;
+}
+int OptAMD_DenseInverseBlocks(long long n, const void* A, int C, long long nPairs, const int* rowElem, const int* colElem,
+                              void* out, int isDouble, long long* info) {
+    if (!A || !info || nPairs < 0 || (nPairs > 0 && !out)) return -1;
+    optamd::DenseSelection sel;
+    if (!sel.build(n, C, nPairs, rowElem, colElem)) return -1;
+    *info = isDouble ? optamd::dense_inverse_blocks_host<double>(n, (const double*)A, sel, (double*)out)
+                     : optamd::dense_inverse_blocks_host<float>(n, (const float*)A, sel, (float*)out);
     return 0;
 }
 int OptAMD_GenericDescribe(const char* filename, char* buf, int n) {

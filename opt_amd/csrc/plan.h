@@ -210,6 +210,14 @@ public:
         (void)line;
         return -1;
     }
+    // Blocks of the inverse of the assembled S or H at the bound unknowns (OptAMD_Covariance):
+    // host element numbers in, a device array of blocks out. 0, -1 a bad index, 1 a plan without
+    // LinearSolver("cholesky"), 2 reason=memory, 3 reason=pivot; `why` holds the message.
+    virtual int covariance(void** params, long long nPairs, const int* rowElem, const int* colElem, void* blocks,
+                           std::string* why) {
+        (void)params; (void)nPairs; (void)rowElem; (void)colElem; (void)blocks; (void)why;
+        return 1;
+    }
     // The explicitly formed H = J^T J (NormalMatrix("explicit"), include/opt_amd.h): the same
     // pair of calls for the normal matrix of a plan whose energy has that statement.
     virtual bool normal_matrix_shape(long long* rows, int* dim, long long* nnzb) const {

@@ -243,6 +243,12 @@ __global__ __launch_bounds__(kBlock) void scale_kernel(long long n, const T* __r
     for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x)
         z[e] = pre[e] * r[e];
 }
+// x = v
+template <typename T>
+__global__ __launch_bounds__(kBlock) void fill_kernel(long long n, T v, T* __restrict__ x) {
+    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x)
+        x[e] = v;
+}
 
 template <class Op>
 class StencilPlan final : public Plan {
@@ -638,10 +644,29 @@ public:
                 *line = "n=" + std::to_string(direct_n_) + " tiles=" + std::to_string(direct_n_ ? dense_tile_count(direct_n_) : 0) +
                         " bytes=" + std::to_string(direct_n_ ? dense_bytes(direct_n_, sizeof(T)) : 0) +
                         " factorisations=" + std::to_string(direct_factorisations_) + " fallbacks=" +
-                        std::to_string(direct_fallbacks_) + " reason=" + direct_reason_ + " min_pivot_ratio=" + ratio;
+                        std::to_string(direct_fallbacks_) + " reason=" + direct_reason_ + " min_pivot_ratio=" + ratio +
+                        " covariances=" + std::to_string(covariances_) + " cov_bytes=" + std::to_string(cov_bytes_);
                 return 0;
             }
         return Plan::direct_info(line);
+    }
+    // Blocks of the inverse of S or H at the bound unknowns (OptAMD_Covariance): the assembly of
+    // explicit_matrix() — on an LM plan with Eliminate without the diagonal in M_e — then dense_fill
+    // without LM's diagonal and with a vector of ones for r, which leaves in the tiles' right-hand
+    // side a 1 per active unknown and a 0 per excluded or held one (the gather's mask), the
+    // factorisation, and DenseFactor's forward chain, Gram tiles and gather. Shares dense_ with
+    // direct_step, which refills it at every Step; writes Ap_ (the ones) and what explicit_matrix()
+    // writes, all rebuilt by the next Step; never delta_, the unknowns, the cost or the LM state.
+    int covariance(void** params, long long nPairs, const int* rowElem, const int* colElem, void* blocks,
+                   std::string* why) override {
+        if constexpr (HasExplicitMatrix<Op>::value) {
+            if (matrix_ == MatrixForm::None || !op_->direct_solver()) return 1;
+            begin_call();
+            const int ret = covariance_body(params, nPairs, rowElem, colElem, (T*)blocks, why);
+            end_call();
+            return ret;
+        }
+        return Plan::covariance(params, nPairs, rowElem, colElem, blocks, why);
     }
     // what the last symbolic phase of S or H did; -1 on a plan with neither statement
     int symbolic_info(std::string* line) const override {
@@ -838,11 +863,11 @@ private:
 
     // the stand-alone reduced entry points' preparation: bind, J^T F and its blocks, the
     // scalar init kernel as in step(), then schur_prepare without the right-hand side
-    void reduced_prepare(void** params) {
+    void reduced_prepare(void** params, bool damped = true) {
         prepare(params);
         red_.ensure(std::max(op_->stencil_blocks(), 4096), 4, kScBase + kSlots * (std::max(0, sp_.lIterations) + 2));
         linear_init(kScTmp, false);   // (its flag exchange is idle here: Eliminate refuses row slabs)
-        schur_prepare(false);
+        schur_prepare(false, damped);
     }
 
     // The linear system of a Step at the current unknowns (PCGInit1 + LM's diagonal): r_ = -J^T F,
@@ -1000,16 +1025,72 @@ private:
         (void)Lit;
         return false;
     }
+    // covariance() between begin_call and end_call (HasExplicitMatrix plans with the statement)
+    int covariance_body(void** params, long long nPairs, const int* rowElem, const int* colElem, T* blocks, std::string* why) {
+        if (matrix_ == MatrixForm::Schur) {
+            reduced_prepare(params, false);
+        } else {
+            prepare(params);
+            op_->jtf(r_, diag_, flags_, stream_);
+            explicit_prepare();
+        }
+        long long rows = 0, nnzb = 0;
+        int dim = 0;
+        if (!op_->matrix_shape(&rows, &dim, &nnzb) || rows * dim < 1) return *why = "covariance: the plan's matrix is empty", -1;
+        const long long n = rows * dim;
+        DenseSelection sel;
+        if (nPairs < 0 || (nPairs > 0 && (!rowElem || !colElem || !blocks)) || !sel.build(n, dim, nPairs, rowElem, colElem))
+            return *why = "covariance: NULL array or element out of range (the matrix has " + std::to_string(rows) + " block rows)", -1;
+        {   // tiles + workspace against the cap, read at every call, and what is still to allocate against the free memory
+            const char* cap = getenv("OPT_AMD_DENSE_MAX_BYTES");
+            const unsigned long long max_bytes = cap && *cap ? strtoull(cap, nullptr, 10) : (2ULL << 30);
+            const size_t tiles = dense_bytes(n, sizeof(T)), ws = dense_cov_bytes(sel, sizeof(T));
+            bool fits = tiles + ws <= max_bytes;
+            if (fits) {
+                size_t free_b = 0, total_b = 0;
+                OPT_HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+                const size_t have = dense_.n() == n ? tiles + (dense_.cov_capacity() == ws ? ws : 0) : 0;
+                const size_t freed = dense_.n() == n ? (dense_.cov_capacity() == ws ? 0 : dense_.cov_capacity())
+                                                     : (dense_.n() ? dense_bytes(dense_.n(), sizeof(T)) + dense_.cov_capacity() : 0);
+                fits = tiles + ws - have <= free_b + freed;
+            }
+            if (!fits)
+                return *why = "covariance: reason=memory: tiles " + std::to_string(tiles) + " + workspace " + std::to_string(ws) +
+                              " bytes exceed OPT_AMD_DENSE_MAX_BYTES or the free device memory", 2;
+            dense_.resize(n);
+            direct_n_ = n;
+            cov_bytes_ = (long long)ws;
+        }
+        tbegin("cov_fill");
+        OPT_HIP_CHECK(hipMemsetAsync(dense_.tiles(), 0, sizeof(T) * (size_t)dense_tile_count(n) * kDenseNB * kDenseNB, stream_));
+        dense_.reset(stream_);
+        hipLaunchKernelGGL((fill_kernel<T>), dim3(fg()), dim3(kBlock), 0, stream_, n_, (T)1, Ap_);
+        op_->dense_fill(nullptr, Ap_, dense_.tiles(), dense_.diag0(), dense_.rhs(), stream_);
+        tend();
+        tbegin("cov_factor"); dense_.factor(stream_); tend();
+        const int fail = dense_.status(stream_, nullptr);
+        if (fail >= 0)
+            return *why = "covariance: reason=pivot row=" + std::to_string(fail) + " element=" + std::to_string(fail / dim) +
+                          " channel=" + std::to_string(fail % dim) + ": the matrix is singular there (gauge freedom?)", 3;
+        tbegin("cov_forward");
+        dense_.cov_begin(sel, stream_);
+        dense_.cov_forward(sel, stream_);
+        tend();
+        tbegin("cov_gram"); dense_.cov_gram(sel, dense_.rhs(), blocks, stream_); tend();
+        ++covariances_;
+        return 0;
+    }
 
     // Schur plans, after the scalar init kernel and before block_init: M_e^-1 in place of the
     // eliminated blocks, b_e stashed and cleared, 1/2 b_e.M^-1 b_e beside q0 (gen_blk_step2's exit
     // test adds it); with `rhs` also r_r -= E M^-1 b_e (b_ too in LM) through one reduced apply
-    // of p = 0 — the caller's delta_, zeroed at the start of the step.
-    void schur_prepare(bool rhs) {
+    // of p = 0 — the caller's delta_, zeroed at the start of the step. `damped` = false leaves LM's
+    // diagonal out of M_e too (covariance(): the undamped S).
+    void schur_prepare(bool rhs, bool damped = true) {
         if constexpr (HasSchur<Op>::value)
             if (schur_) {
                 tbegin("schur_rhs");
-                op_->schur_rhs(CtC_, r_, b_, lm_ ? 1 : 0, red_.slot(nb(), kScQc), stream_);
+                op_->schur_rhs(CtC_, r_, b_, lm_ && damped ? 1 : 0, red_.slot(nb(), kScQc), stream_);
                 if (rhs) {
                     op_->schur_apply(delta_, Ap_, nullptr, nullptr, red_.slot(nb(), kScTmp), stream_);
                     hipLaunchKernelGGL((schur_sub_kernel<T>), dim3(fg()), dim3(kBlock), 0, stream_, n_, r_, (const T*)Ap_,
@@ -1354,6 +1435,7 @@ private:
     T *w_ = nullptr, *be_ = nullptr;           // compact (eliminated elements): M^-1-sized products, the stash of b_e
     DenseFactor<T> dense_;                     // LinearSolver("cholesky"): the tiles, allocated at the first direct Step
     long long direct_n_ = 0, direct_factorisations_ = 0, direct_fallbacks_ = 0;
+    long long covariances_ = 0, cov_bytes_ = 0;   // covariance(): calls completed, the last workspace
     double direct_ratio_ = INFINITY;
     const char* direct_reason_ = "none";
     MatrixForm matrix_ = MatrixForm::None;     // S or H assembled per step, the apply a block SpMV (HasExplicitMatrix)
